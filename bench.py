@@ -29,7 +29,15 @@ Workloads (--workload; the default cfg3 line is the metric line):
             one segmented silhouette launch set (ccg_silhouette_segments_dev),
             map-back and per-subcluster co-clusters.
 
-Usage: python bench.py [--gpus N --steps K --warmup W].  With --gpus N > 1
+Usage: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+[--full].  A plain run does only what the headline figure needs: it builds
+the inputs, warms up, times the K steps, writes the last timed step's outputs
+(--dump-outputs) and prints the result line.  --full adds everything else
+the benchmark measures, outside the timed region: the certification
+statistics, the per-kernel and per-phase times of one extra step, the stages' rooflines
+measured in isolation, the drop-in's host SNN path, the CPU baseline and the
+oracle check of a timed launch set (--no-cpu-baseline / --check select those
+two legs).  With --gpus N > 1
 and no WORLD_SIZE in the environment, this process (which never touches the
 GPU) starts N ranks through torch.distributed.run (127.0.0.1) and exits with
 their status; under torch.distributed.run (WORLD_SIZE set) each rank drives
@@ -79,8 +87,18 @@ def parse():
     ap.add_argument("--pcs", type=int, default=None)
     ap.add_argument("--genes", type=int, default=2000)
     ap.add_argument("--boots-per-gpu", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="outside the timed region also measure and check everything beyond the headline figure: "
+                         "certification statistics, per-kernel and per-phase times of one extra step, the "
+                         "stages' rooflines in isolation, the host SNN path, the CPU baseline and the oracle "
+                         "check; off by default")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed (silhouette scores, "
+                         "selection, assignment columns, co-cluster counts, and the kNN / SNN class rows left in "
+                         "the launch-set buffers) as DIR/<name>.npy in float64; outputs larger than the per-array "
+                         "cap are a fixed, seeded sample of their entries")
     ap.add_argument("--check", action="store_true",
-                    help="with the CPU baseline leg: also check one bootstrap's outputs against the oracle "
+                    help="(--full) with the CPU baseline leg: also check one bootstrap's outputs against the oracle "
                          "(on by default with the CPU baseline)")
     ap.add_argument("--boot-size", type=float, default=0.9)
     ap.add_argument("--cpu-sample-rows", type=int, default=6000)
@@ -120,6 +138,10 @@ def parse():
     ap.add_argument("--launcher-check", action="store_true",
                     help="only start the ranks, all-gather their ids over gloo and print them (no GPU)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.check and not a.full:
+        ap.error("--check is part of the --full run")
     w = WORKLOADS[a.workload]
     for k in ("cells", "pcs", "boots_per_gpu"):
         if getattr(a, k) is None:
@@ -541,6 +563,62 @@ def decode_class_rows(row_class, u, off, ln, nbr, wpk, ks, c0=0):
     return out
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs: all arrays together stay below this (float64 entries)
+
+
+def _dump_pick(torch, flat, cap, name):
+    """All of a flat device tensor, or a fixed sample of cap entries (sorted
+    positions drawn by default_rng(crc32(name)): the same for every run)."""
+    import zlib
+    if flat.numel() <= cap:
+        return flat
+    pos = np.sort(np.random.default_rng(zlib.crc32(name.encode())).integers(0, flat.numel(), cap))
+    return flat[torch.from_numpy(pos).to(flat.device)]
+
+
+def _dump_class_rows(torch, sb, u):
+    """The used entries of a SnnBufs' class rows as flat tensors (partners,
+    packed weights): the capacity-based rows hold unwritten gaps."""
+    lens = sb.ln[:u].long()
+    first = torch.cumsum(lens, 0) - lens
+    pos = torch.repeat_interleave(sb.off[:u] - first, lens) + torch.arange(int(lens.sum().item()), device=lens.device)
+    return sb.nbr[pos], sb.wpk[pos]
+
+
+def dump_outputs(torch, path, named, slots):
+    """--dump-outputs: named = {name: device tensor} of a step's results;
+    slots = [(slot, rows, knn, SnnBufs, info row)] for the launch-set buffers
+    as the last timed step left them.  Everything is written as float64
+    DIR/<name>.npy; int16 co-cluster counts are read as uint16."""
+    torch.cuda.synchronize()
+    arrs = dict(named)
+    for si, m, knn, sb, info in slots:
+        u = int(info[0].item())
+        arrs[f"knn_slot{si}"] = knn[:m]
+        arrs[f"snn_row_class_slot{si}"] = sb.row_class[:m]
+        arrs[f"snn_class_root_slot{si}"] = sb.class_root[:u]
+        arrs[f"snn_class_len_slot{si}"] = sb.ln[:u]
+        if int(info[3:].min().item()) >= 0:  # (rows are written only when they fit)
+            arrs[f"snn_class_nbr_slot{si}"], arrs[f"snn_class_wpk_slot{si}"] = _dump_class_rows(torch, sb, u)
+    cap = max(1, DUMP_BYTES // 8 // max(len(arrs), 1))
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrs.items():
+        v = _dump_pick(torch, t.reshape(-1), cap, name)
+        if v.dtype == torch.int16:
+            v = v.to(torch.int32) & 0xFFFF
+        np.save(os.path.join(path, name + ".npy"), v.to(torch.float64).cpu().numpy())
+
+
+def ring_slots(S, count, rows_of, knn_s, snn_s, snn_info):
+    """The launch-set buffers after a step: slot si holds the last set t (of
+    count) with t % S == si."""
+    out = []
+    for si in range(min(S, count)):
+        t = si + ((count - 1 - si) // S) * S
+        out.append((si, rows_of(t), knn_s[si], snn_s[si], snn_info[t]))
+    return out
+
+
 class SnnBufs:
     """Output buffers of one in-flight SNN pass at the level of row classes
     (ccg_snn_classes_dev: the kernels both drop-ins run through
@@ -752,6 +830,57 @@ def run_cfg5(args, torch, dist, grp, engs, dev, world, rank, json_fd, ranks_seen
     torch.cuda.synchronize()
     barrier()
     el = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        named = {}
+        for c in range(nsub):
+            named.update({f"sil_means_sub{c}": means[c], f"sil_nclust_sub{c}": nclust[c],
+                          f"sil_minsize_sub{c}": minsize[c], f"assignments_sub{c}": A[c],
+                          f"cocluster_co_sub{c}": co[c], f"cocluster_both_sub{c}": both[c]})
+        named["snn_info"] = snn_info
+        dump_outputs(torch, args.dump_outputs, named,
+                     ring_slots(S, len(batches), lambda t: int(plans[t][1][-1]), knn_s, snn_s, snn_info))
+    head = {
+        "metric": METRIC,
+        "unit": "bootstraps/s",
+        "n_gpus": G,
+        "ranks_seen": ranks_seen,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "dtype_detail": "kNN order exact in f64 (segmented distinct-cell screen: fp16 hi/lo x3 MFMA, f64 certify, "
+                        "exact f64 expansion); silhouette f64 fixed-point sums; co-cluster int8 MFMA",
+        "data": "synthetic: NB counts (12 populations, 2000 genes) -> PCA, subclusters = random cell blocks of "
+                "5k-20k cells with the first d_c PCs; synthetic clusterings (C 2..20) in place of host Leiden",
+        "config": {
+            "workload": f"BASELINE cfg5: one iterate=TRUE level on {N} cells -- {nsub} subclusters "
+                        f"({min(sizes)}-{max(sizes)} cells, pcNum {min(dcs)}-{max(dcs)}), {B} bootstraps of every "
+                        f"subcluster per GPU per step (value = level bootstraps/s; x{nsub} subcluster-bootstraps), "
+                        f"{SB} bootstraps x {nsub} subclusters per segmented launch set",
+            "name": "cfg5", "cells": N, "subcluster_cells": sizes, "subcluster_pcs": dcs, "boots_per_gpu": B,
+            "segments_per_launch": SB * nsub, "streams_per_gpu": S,
+        },
+        "full": bool(args.full),
+    }
+    if not args.full:  # the plain run: the headline figure only
+        per_rank = per_rank_steps(torch, dist, G, el / args.steps * 1000, dev)
+        if G > 1:
+            tt = torch.tensor([el], dtype=torch.float64, device=dev)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            el = tt.item()
+        value = G * B * args.steps / el
+        out = dict(head, value=round(value, 3), ms_per_step=round(el / args.steps * 1000, 3),
+                   subcluster_bootstraps_per_s=round(value * nsub, 3), per_rank=per_rank)
+        if rank == 0:
+            os.write(json_fd, (json.dumps(out) + "\n").encode())
+        for e in engs[1:]:
+            e.close()
+        grp.close()
+        if G > 1:
+            dist.destroy_process_group()
+        return
     # kernel times (library timers) over one more step, then the segmented kNN in isolation
     for e in engs:
         e.timing(True)
@@ -806,37 +935,15 @@ def run_cfg5(args, torch, dist, grp, engs, dev, world, rank, json_fd, ranks_seen
         "knn_total_ms_per_step": round(iso_tot[0], 3),
         "exact_search_rows_per_step": int(fbk),
     }
-    out = {
-        "metric": METRIC,
+    out = dict(head, **{
         "value": round(value, 3),
-        "unit": "bootstraps/s",
-        "n_gpus": G,
-        "ranks_seen": ranks_seen,
-        "steps": args.steps,
-        "warmup": args.warmup,
         "ms_per_step": round(el / args.steps * 1000, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "dtype_detail": "kNN order exact in f64 (segmented distinct-cell screen: fp16 hi/lo x3 MFMA, f64 certify, "
-                        "exact f64 expansion); silhouette f64 fixed-point sums; co-cluster int8 MFMA",
-        "data": "synthetic: NB counts (12 populations, 2000 genes) -> PCA, subclusters = random cell blocks of "
-                "5k-20k cells with the first d_c PCs; synthetic clusterings (C 2..20) in place of host Leiden",
-        "config": {
-            "workload": f"BASELINE cfg5: one iterate=TRUE level on {N} cells -- {nsub} subclusters "
-                        f"({min(sizes)}-{max(sizes)} cells, pcNum {min(dcs)}-{max(dcs)}), {B} bootstraps of every "
-                        f"subcluster per GPU per step (value = level bootstraps/s; x{nsub} subcluster-bootstraps), "
-                        f"{SB} bootstraps x {nsub} subclusters per segmented launch set",
-            "name": "cfg5", "cells": N, "subcluster_cells": sizes, "subcluster_pcs": dcs, "boots_per_gpu": B,
-            "segments_per_launch": SB * nsub, "streams_per_gpu": S,
-        },
         "subcluster_bootstraps_per_s": round(value * nsub, 3),
         "per_rank": per_rank,
         "roofline": roof,
         "kernel_ms_per_step": {w: round(v[0], 3) for w, v in kt.items()},
         "kernel_launches_per_step": {w: int(v[1]) for w, v in kt.items()},
-    }
+    })
     if rank == 0 and G == 1 and not args.no_cpu_baseline:
         dm = int(round(float(np.mean(dcs))))
         out["cpu_baseline"] = cpu_baseline(pcs[:, :dm].contiguous().cpu().numpy(), B, max(ns), N, dm,
@@ -884,6 +991,13 @@ def per_rank_report(torch, dist, world, values, dev=None):
         got = [t]
     return [dict({"rank": r}, **{k: round(float(v), 3) for k, v in zip(PHASES, g.tolist())})
             for r, g in enumerate(got)]
+
+
+def per_rank_steps(torch, dist, world, step_ms, dev):
+    """The plain run's per_rank: every rank's own timed-region step only (the
+    phases come from the extra timer step of a --full run)."""
+    return [{"rank": r["rank"], "step_ms": r["step_ms"]}
+            for r in per_rank_report(torch, dist, world, {"step_ms": step_ms}, dev)]
 
 
 def visible_gpus():
@@ -1174,11 +1288,12 @@ def main():
         for k in range(1, emul):
             A_full[k * cpr:(k + 1) * cpr] = torch.roll(A_local, shifts=k * 7919, dims=1)
         torch.cuda.synchronize()
-    eng.gather_rows_rm_t(pcs, N, d, boots[0], rows)
-    fb = eng.knn_boot_hint_t(pcs_cm, N, d, boots[0], uniq[0], rows, 20, knn, hint, stats=True)  # certification statistics
-    fb_cold = eng.knn_boot_t(pcs_cm, N, d, boots[0], uniq[0], rows, 20, knn, stats=True)
-    fb_tab_build = eng.knn_table_t(pcs_cm, N, d, KT, tab_idx, tab_d2, stats=True)
-    fb_tab = eng.knn_boot_table_t(pcs_cm, N, d, boots[0], uniq[0], rows, 20, tab_idx, tab_d2, knn, stats=True)
+    if args.full:  # certification statistics
+        eng.gather_rows_rm_t(pcs, N, d, boots[0], rows)
+        fb = eng.knn_boot_hint_t(pcs_cm, N, d, boots[0], uniq[0], rows, 20, knn, hint, stats=True)
+        fb_cold = eng.knn_boot_t(pcs_cm, N, d, boots[0], uniq[0], rows, 20, knn, stats=True)
+        fb_tab_build = eng.knn_table_t(pcs_cm, N, d, KT, tab_idx, tab_d2, stats=True)
+        fb_tab = eng.knn_boot_table_t(pcs_cm, N, d, boots[0], uniq[0], rows, 20, tab_idx, tab_d2, knn, stats=True)
 
     # --launch graph: capture the bootstrap phase once, after every untimed
     # call above (the warmup and the statistics calls sized every workspace:
@@ -1225,6 +1340,72 @@ def main():
     el = time.perf_counter() - t0
     host_ms = host_t[0] / args.steps * 1000
     ring_ms = sum(e.timing_read("host_ring_wait")[0] for e in ring_engs) / args.steps
+    if args.dump_outputs and rank == 0:
+        named = {"knn_table_idx": tab_idx, "knn_table_d2": tab_d2, "snn_info": snn_info,
+                 "assignments": A_local, "cocluster_co": co, "cocluster_both": both}
+        if not use_table:
+            del named["knn_table_idx"], named["knn_table_d2"]
+        if robust:  # granular mode scores and selects nothing
+            named.update({"sil_means": means, "sil_nclust": nclust, "sil_minsize": minsize, "choice": choice})
+        dump_outputs(torch, args.dump_outputs, named,
+                     ring_slots(S, len(batches) if batched else B, lambda t: sets[t]["m"] if batched else n,
+                                knn_s, snn_out, snn_info))
+    head = {
+        "metric": METRIC,
+        "unit": "bootstraps/s",
+        "n_gpus": G,
+        "ranks_seen": ranks_seen,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "dtype_detail": ("kNN order exact in f64 (cell table over all cells once per step: fp16 hi/lo x3 MFMA "
+                         "screen, f32 accumulate, f64 certify; per bootstrap the table's present entries, exact "
+                         "f64 search for cells short of kq, exact f64 expansion to rows); " if use_table else
+                         "kNN order exact in f64 (distinct cells: fp16 hi/lo x3 MFMA screen, f32 accumulate, "
+                         "f64 certify, exact f64 expansion to rows; screen warm-started by earlier bootstraps' "
+                         "certified distances); ") +
+                        "silhouette f64 with fixed-point sums; co-cluster int8 MFMA, int32 counts",
+        "data": "synthetic: NB counts (12 populations, 2000 genes) -> PCA; synthetic clusterings in place of host Leiden",
+        "config": {
+            "workload": workload_text(args.workload, N, d, B, G, emul),
+            "name": args.workload,
+            "mode": W["mode"], "assignment_columns": Gc * cpr, "slab_rows": [int(r0), int(r1)],
+            "cells": N, "pcs": d, "bootstrap_rows": n, "distinct_cells_mean": round(float(np.mean(uniq)), 1),
+            "boots_per_gpu": B, "clusterings_per_boot": L,
+            "parallelism": f"bootstraps x{G}, co-cluster row slabs x{G}", "streams_per_gpu": S,
+            "knn_path": args.knn_path, "silhouette_streams": len(streams_sil),
+        },
+        "full": bool(args.full),
+        "launch": launch_note,
+        "host_enqueue_ms_per_step": round(host_ms, 3),
+        "host_ring_wait_ms_per_step": round(ring_ms, 3),
+        "host_launch_ms_per_step": round(host_ms - ring_ms, 3),
+        "host_enqueue_note": "host time in the step's launch loop; of it, host_ring_wait is time blocked on the "
+                             "pinned upload ring (the host is that many launch sets ahead of the GPU: "
+                             "back-pressure), host_launch the rest (issuing work)",
+        "boots_per_launch_set": NBB,
+        "launch_sets_per_step": len(batches) if batched else B,
+        ("snn_class_edges_max_per_launch_set" if batched else "snn_class_edges_max_per_boot"): [int(e) for e in need],
+    }
+    if not args.full:  # the plain run: the headline figure only
+        per_rank = per_rank_steps(torch, dist, G, el / args.steps * 1000, dev)
+        if G > 1:
+            t = torch.tensor([el], dtype=torch.float64, device=dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            el = t.item()
+        out = dict(head, value=round(G * B * args.steps / el, 3), ms_per_step=round(el / args.steps * 1000, 3),
+                   per_rank=per_rank)
+        if rank == 0:
+            os.write(json_fd, (json.dumps(out) + "\n").encode())
+        for e in engs[1:]:
+            e.close()
+        grp.close()
+        if G > 1:
+            dist.destroy_process_group()
+        return
     # kernel-time breakdown: one more (untimed) step with the library's
     # hipEvent timers on
     for e in engs + engs_sil:
@@ -1483,36 +1664,9 @@ def main():
                                   f"cells against every present centroid of the 60 labelings)",
         "ms_per_boot": round(sil_ms, 4),
     }
-    out = {
-        "metric": METRIC,
+    out = dict(head, **{
         "value": round(value, 3),
-        "unit": "bootstraps/s",
-        "n_gpus": G,
-        "ranks_seen": ranks_seen,
-        "steps": args.steps,
-        "warmup": args.warmup,
         "ms_per_step": round(el / args.steps * 1000, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "dtype_detail": ("kNN order exact in f64 (cell table over all cells once per step: fp16 hi/lo x3 MFMA "
-                         "screen, f32 accumulate, f64 certify; per bootstrap the table's present entries, exact "
-                         "f64 search for cells short of kq, exact f64 expansion to rows); " if use_table else
-                         "kNN order exact in f64 (distinct cells: fp16 hi/lo x3 MFMA screen, f32 accumulate, "
-                         "f64 certify, exact f64 expansion to rows; screen warm-started by earlier bootstraps' "
-                         "certified distances); ") +
-                        "silhouette f64 with fixed-point sums; co-cluster int8 MFMA, int32 counts",
-        "data": "synthetic: NB counts (12 populations, 2000 genes) -> PCA; synthetic clusterings in place of host Leiden",
-        "config": {
-            "workload": workload_text(args.workload, N, d, B, G, emul),
-            "name": args.workload,
-            "mode": W["mode"], "assignment_columns": Gc * cpr, "slab_rows": [int(r0), int(r1)],
-            "cells": N, "pcs": d, "bootstrap_rows": n, "distinct_cells_mean": round(float(np.mean(uniq)), 1),
-            "boots_per_gpu": B, "clusterings_per_boot": L,
-            "parallelism": f"bootstraps x{G}, co-cluster row slabs x{G}", "streams_per_gpu": S,
-            "knn_path": args.knn_path, "silhouette_streams": len(streams_sil),
-        },
         "roofline": roof_coc,
         "roofline_note": "the co-cluster GEMM is the largest single launch of a step; the per-bootstrap "
                          "stages follow (kNN table screen once per step, SNN, silhouette)",
@@ -1528,16 +1682,7 @@ def main():
                          "phases come from torch-stream events in the extra timer step: the bootstrap loop, "
                          "selection + map-back, the RCCL all-gather of the assignment columns, this rank's "
                          "co/both row slab",
-        "launch": launch_note,
-        "host_enqueue_ms_per_step": round(host_ms, 3),
-        "host_ring_wait_ms_per_step": round(ring_ms, 3),
-        "host_launch_ms_per_step": round(host_ms - ring_ms, 3),
-        "host_enqueue_note": "host time in the step's launch loop; of it, host_ring_wait is time blocked on the "
-                             "pinned upload ring (the host is that many launch sets ahead of the GPU: "
-                             "back-pressure), host_launch the rest (issuing work)",
         "host_launch_ms_per_boot_idle_gpu": round(host_idle_ms, 3),
-        "boots_per_launch_set": NBB,
-        "launch_sets_per_step": len(batches) if batched else B,
         "host_snn_pass_ms_per_boot": round(1e3 * host_snn[0], 2),
         "host_snn_decode_ms_per_boot": round(1e3 * host_snn[1], 2),
         "host_snn_note": "the drop-in's host consumer path for one bootstrap (Engine.snn_multi: ccg_snn_graphs_cells "
@@ -1546,8 +1691,7 @@ def main():
         "cocluster_avg_ms": round(coc_ms, 3),
         "knn_fallback_rows_last_boot": int(fb[1]),
         "knn_fallback_rows_last_boot_cold": int(fb_cold[1]),
-        ("snn_class_edges_max_per_launch_set" if batched else "snn_class_edges_max_per_boot"): [int(e) for e in need],
-    }
+    })
     if rank == 0 and G == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(pcs.cpu().numpy(), B, n, N, d, args.cpu_sample_rows, robust=robust,
                                            coc_cols=Gc * cpr, coc_pairs=P)

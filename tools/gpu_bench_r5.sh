@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT/gpurun_out/$OUT
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $R/smoke.log 2>&1 || exit $?
 timeout -k 10 240 python tools/boot_micro.py > $R/boot_micro.json 2> $R/boot_micro.err || exit $?
-timeout -k 10 400 python bench.py --steps ${BSTEPS:-5} --warmup 1 ${BENCH_EXTRA:-} > $R/bench.json 2> $R/bench.err || exit $?
+timeout -k 10 400 python bench.py --steps ${BSTEPS:-5} --warmup 1 --full ${BENCH_EXTRA:-} > $R/bench.json 2> $R/bench.err || exit $?
 if [ -z "$NO_EAGER" ]; then
 timeout -k 10 400 python bench.py --steps ${BSTEPS:-5} --warmup 1 --launch eager --no-cpu-baseline > $R/bench_eager.json 2> $R/bench_eager.err || exit $?
 fi

@@ -11,7 +11,7 @@ mkdir -p $R
 export TMPDIR=/tmp
 echo "$(date +%T) start" > $R/progress.log
 for w in ${WLS:-cfg3 cfg3job cfg2 cfg4 cfg5}; do
-  X="--no-cpu-baseline"; [ $w = cfg3 ] && X=""
+  X="--full --no-cpu-baseline"; [ $w = cfg3 ] && X="--full"
   echo "$(date +%T) bench $w" >> $R/progress.log
   timeout -k 10 ${BT:-420} python bench.py --workload $w --steps ${BSTEPS:-5} --warmup 1 $X \
       > $R/bench_$w.json 2> $R/bench_$w.err || exit $?

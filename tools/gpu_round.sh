@@ -20,7 +20,7 @@ src=$?; echo "smoke rc=$src" >> $R/smoke.log
 fi
 for w in ${WORKLOADS:-}; do
   timeout -k 10 ${BENCH_TIMEOUT:-400} python bench.py --workload $w --steps ${BSTEPS:-3} --warmup 1 \
-      ${BENCH_EXTRA:---no-cpu-baseline} > $R/bench_$w.json 2> $R/bench_$w.err
+      --full ${BENCH_EXTRA:---no-cpu-baseline} > $R/bench_$w.json 2> $R/bench_$w.err
   brc=$?; echo "bench rc=$brc" >> $R/bench_$w.err
   [ $brc -ne 0 ] && exit $brc
 done

@@ -18,6 +18,6 @@ if [ -z "$NO_MICRO" ]; then
 timeout -k 10 240 python tools/boot_micro.py > $R/boot_micro.json 2> $R/boot_micro.err || exit $?
 fi
 if [ -z "$NO_BENCH" ]; then
-timeout -k 10 400 python bench.py --steps ${BSTEPS:-5} --warmup 1 ${BENCH_EXTRA:---no-cpu-baseline} > $R/bench.json 2> $R/bench.err || exit $?
+timeout -k 10 400 python bench.py --steps ${BSTEPS:-5} --warmup 1 --full ${BENCH_EXTRA:---no-cpu-baseline} > $R/bench.json 2> $R/bench.err || exit $?
 fi
 exit 0
