@@ -27,6 +27,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "ccg_internal.h"
@@ -232,10 +233,19 @@ __global__ void sil_quant(const double* __restrict__ x, int64_t m, int d, const 
     // rounding (with |x|^2 of the raw row, a singleton's v_c was the
     // quantisation residue 2 |x| 2^-e).  Its DMAX threads are DMAX-aligned
     // lanes of one wave (fixed xor tree: deterministic).
+    // The first level is fma(vq, vq, the partner's rounded square): what the
+    // compiler's contraction has always made of "s2 = vq * vq; s2 += shfl(s2)"
+    // here, now written out so that the bits do not hang on it and
+    // sil_quant_row (one thread per row, the MFMA sums) can state the same
+    // tree.  Lane 0 of a row adds lanes k < DMAX / 2 only from there on.
+    // (The contraction was there in all three instances, DMAX 16, 32 and 64;
+    // the outputs of d = 8, 12, 30, 32 and 40 calls hash equal before and
+    // after writing it out.)
     const double vq = (double)qv / sc;
-    double s2 = vq * vq;
+    const double sq = vq * vq;
+    double s2 = fma(vq, vq, __shfl_xor(sq, DMAX / 2, 64));
 #pragma unroll
-    for (int o = DMAX / 2; o > 0; o >>= 1) s2 += __shfl_xor(s2, o, 64);
+    for (int o = DMAX / 4; o > 0; o >>= 1) s2 += __shfl_xor(s2, o, 64);
     if (k == 0) q2[r] = __double2ll_rn(s2 * ldexp(1.0, scale_exp(sil_s2_bound(maxabs, d, m))));
 }
 
@@ -421,6 +431,316 @@ __global__ void sil_sums_exc(int64_t m, int d, const int32_t* __restrict__ label
         atomicAdd(&gsum2[lv * (cmax + 1) + lab], (unsigned long long)q2[r]);
         atomicAdd(&gcnt[lv * (cmax + 1) + lab], 1ull);
     }
+}
+
+// ------------------------------------------ sums on the matrix core --
+// K1 (d <= 32, cmax <= SIL_MCMAX): the same S1, S2 and counts as
+// sil_sums_blk, as a one-hot GEMM.  For a tile of SIL_MT positions and
+// labeling l,  sums[c][col] = sum_p A_l[c][p] B[p][col]  with
+//   A_l[c][p] = w_l[p] if lab_l[p] == c else 0          (int8, built in registers)
+//   B[p][col] = the fixed-point value of column col in [d dims | S2 | 1]
+// written as NL balanced base-256 digits in [-128, 127] (v = sum_j d_j 256^j;
+// |v| <= 2^61 / m, so NL = sil_mfma_limbs(m) <= 8 digits hold it).  Limb j of
+// the 32 columns is one B operand of v_mfma_i32_32x32x32_i8, so a lane's
+// accumulator register r of limb j holds limb j of the same (cluster,
+// column) for every j, and the int64 sum is recombined in the lane:
+// sum_j acc_j 2^(8j) in wrapping 64-bit arithmetic.  Exact: an int32
+// accumulator sums at most SIL_MT products of magnitude <= 127 x 128, the
+// true int64 sum fits by the scale rule, and integer sums in any order give
+// the bits of the scatter path.
+// A block quantises its tile's rows from x (no q1/q2 round trip through
+// memory), writes their limbs to LDS once ([limb][column][position] bytes,
+// column stride SIL_MSTR so a K-step's 16-byte reads spread over the banks)
+// and, after one barrier, its 8 waves take the L labelings of the tile from
+// an LDS counter: a wave stages the labeling's codes and weights as bytes in
+// its own LDS slice (code 0: positions past the tile, codes outside
+// [1, cmax], weight <= 0), runs the K loop per block of 32 clusters (only up
+// to the largest code present) and adds every non-zero (cluster, column)
+// sum to the global sums with one atomic; no block barrier per labeling.
+// The rows are read once per call, so the XCD-aware tile order of
+// sil_sums_blk (which kept its 15 re-reads in one L2) has nothing left to
+// serve and is not kept.  A weight above 127 (a cell with more than 127
+// copies) does not fit the int8 operand: that position contributes 0 to the
+// GEMM and its row is added by int64 atomics (sil_add_row) by the lane that
+// staged it.  d = 31, 32: columns 32 .. d + 1 take a second pass of the block
+// over a second column tile (only those columns are staged again).  Grid: x =
+// tiles; y = blocks sharing a tile's labelings (block y takes y, y + gridDim.y,
+// ...), more than one only when the tiles alone would not cover the CUs.
+#define SIL_MT 512                 // positions per tile (an int32 accumulator allows 2^16)
+#define SIL_MB 512                 // threads: 8 waves
+#define SIL_MSTR (SIL_MT + 16)     // bytes between columns of a limb in LDS
+#define SIL_MCMAX 255              // codes are staged as bytes
+typedef int sil_v4i __attribute__((ext_vector_type(4)));
+typedef int sil_v16i __attribute__((ext_vector_type(16)));
+static_assert(SIL_SP % SIL_MT == 0, "a segment's sums tiles split into whole MFMA tiles");
+static_assert(SIL_MT == SIL_MB, "one position per thread while staging");
+
+__host__ __device__ inline size_t sil_mfma_lds(int NL) {
+    return (size_t)NL * 32 * SIL_MSTR + 2 * SIL_MT * sizeof(int) + (SIL_MB / 64) * 2 * SIL_MT + 16;
+}
+// balanced base-256 digits needed for |v| <= 2^61 / m (twice that is kept:
+// NL digits reach 127 (256^NL - 1) / 255 > 2^(8 NL - 2))
+static inline int sil_mfma_limbs(int64_t m) {
+    int lg = 0;
+    while ((m >> (lg + 1)) > 0) ++lg;  // floor(log2 m)
+    return (61 - lg + 2 + 7) / 8;
+}
+
+// The fixed-point row of sil_quant, by one thread: q[k] = round(x_k sc) and
+// the return value q2 = round(|x_q|^2 sc2), the squares summed as lane 0 of
+// sil_quant's xor tree sums them (offsets DMAX/2 .. 1): the first level
+// fma(vq_k, vq_k, round(vq_{k + DMAX/2}^2)) for k < DMAX / 2, then
+// s[k] + s[k + o] level by level (fp64 adds commute, so this serial form
+// gives the tree's bits).  Nothing else is contracted.
+template <int DMAX>
+__device__ __forceinline__ long long sil_quant_row(const double* __restrict__ xr, int d, double sc, double inv_sc,
+                                                   double sc2, long long (&q)[DMAX]) {
+#pragma clang fp contract(off)
+    double vq[DMAX], s[DMAX / 2];
+#pragma unroll
+    for (int k = 0; k < DMAX; ++k) {
+        q[k] = k < d ? __double2ll_rn(xr[k] * sc) : 0ll;
+        vq[k] = (double)q[k] * inv_sc;  // (exact: a power of two, as sil_quant's division)
+    }
+#pragma unroll
+    for (int k = 0; k < DMAX / 2; ++k) s[k] = fma(vq[k], vq[k], vq[k + DMAX / 2] * vq[k + DMAX / 2]);
+#pragma unroll
+    for (int o = DMAX / 4; o > 0; o >>= 1)
+#pragma unroll
+        for (int k = 0; k < o; ++k) s[k] = s[k] + s[k + o];
+    return __double2ll_rn(s[0] * sc2);
+}
+
+// w copies of row r added to cluster lab of one labeling by int64 atomics
+// (gs: the cluster's d sums; g2, gc: its S2 and count), quantised on the fly.
+template <int DMAX>
+__device__ __noinline__ void sil_add_row(const double* __restrict__ x, int64_t r, int d, int64_t m, double maxabs,
+                                         long long w, unsigned long long* __restrict__ gs,
+                                         unsigned long long* __restrict__ g2, unsigned long long* __restrict__ gc) {
+    const int e = scale_exp(maxabs * (double)m);
+    long long q[DMAX];
+    const long long q2 = sil_quant_row<DMAX>(x + r * d, d, ldexp(1.0, e), ldexp(1.0, -e),
+                                             ldexp(1.0, scale_exp(sil_s2_bound(maxabs, d, m))), q);
+#pragma unroll
+    for (int k = 0; k < DMAX; ++k)
+        if (k < d) atomicAdd(&gs[k], (unsigned long long)(w * q[k]));
+    atomicAdd(g2, (unsigned long long)(w * q2));
+    atomicAdd(gc, (unsigned long long)w);
+}
+
+template <int DMAX, int NL, bool SEG>
+__global__ __launch_bounds__(SIL_MB) void sil_sums_mfma(const double* __restrict__ x, int64_t m, int d,
+                                                        const int32_t* __restrict__ labels, int L, int cmax,
+                                                        const unsigned* __restrict__ maxabs_bits,
+                                                        unsigned long long* __restrict__ gsum,
+                                                        unsigned long long* __restrict__ gsum2,
+                                                        unsigned long long* __restrict__ gcnt,
+                                                        const int* __restrict__ rep, const int* __restrict__ mult,
+                                                        const int* __restrict__ cnt, int64_t mw,
+                                                        const int64_t* __restrict__ nrep,
+                                                        const int64_t* __restrict__ scan, SilSegs sgs) {
+    static_assert(DMAX <= 32, "at most two column tiles");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned char* bq = smem;                                          // [NL][32][SIL_MSTR]
+    int* srow = (int*)(smem + (size_t)NL * 32 * SIL_MSTR);             // [SIL_MT] the positions' rows
+    int* scnt = srow + SIL_MT;                                         // [SIL_MT] their cells' copies
+    unsigned char* swl = (unsigned char*)(scnt + SIL_MT);              // per wave: codes [SIL_MT], weights [SIL_MT]
+    int* snext = (int*)(swl + (SIL_MB / 64) * 2 * SIL_MT);             // [2] next labeling, per column tile
+    constexpr int NCT = (DMAX + 2 + 31) / 32;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5;
+    int64_t rb, npos;  // the tile's first position, the end of its positions
+    int q = 0;
+    if constexpr (SEG) {  // SIL_SP / SIL_MT tiles per sums tile of the segment table
+        constexpr int SUB = SIL_SP / SIL_MT;
+        const int tile = blockIdx.x / SUB;
+        q = sil_seg_tile(sgs.ts, sgs.nseg, tile);
+        rb = scan[sgs.off[q]] + (int64_t)(tile - sgs.ts[q]) * SIL_SP + (int64_t)(blockIdx.x % SUB) * SIL_MT;
+        npos = scan[sgs.off[q + 1]];
+    } else {
+        rb = (int64_t)blockIdx.x * SIL_MT;
+        npos = rep ? *nrep : m;
+    }
+    if (rb >= npos) return;
+    const int nval = (int)min((int64_t)SIL_MT, npos - rb);
+    const double maxabs = (double)__uint_as_float(*maxabs_bits);
+    // this thread's position: its row, fixed point
+    const bool valid = tid < nval;
+    const int myrow = valid ? (rep ? rep[rb + tid] : (int)(rb + tid)) : 0;
+    srow[tid] = myrow;
+    scnt[tid] = (valid && rep) ? cnt[rb + tid] : 1;
+    if (tid < 2) snext[tid] = 0;
+    long long qr[DMAX];
+    long long q2 = 0;
+    if (valid) {
+        const int e = scale_exp(maxabs * (double)m);
+        q2 = sil_quant_row<DMAX>(x + (int64_t)myrow * d, d, ldexp(1.0, e), ldexp(1.0, -e),
+                                 ldexp(1.0, scale_exp(sil_s2_bound(maxabs, d, m))), qr);
+    } else {
+#pragma unroll
+        for (int k = 0; k < DMAX; ++k) qr[k] = 0;
+    }
+    unsigned char* wl = swl + wave * 2 * SIL_MT;
+    unsigned char* ww = wl + SIL_MT;
+    const int nks = (nval + 31) >> 5;  // K-steps of 32 positions
+    // one pass over column tile CT: columns 32 CT .. 32 CT + 31 of [d dims | S2 | 1]
+    auto pass = [&](auto CT) {
+        constexpr int ct = decltype(CT)::value;
+#pragma unroll
+        for (int c = 0; c < 32; ++c) {
+            const int col = ct * 32 + c;
+            // (columns past d + 1 are not staged: their bytes are whatever the
+            // LDS held, and their sums are not flushed)
+            if (col >= DMAX + 2 || col >= d + 2) continue;
+            long long v = 0;
+            if (col < DMAX) v = qr[col < DMAX ? col : 0];  // (zero past d)
+            if (col == d) v = q2;
+            if (col == d + 1) v = valid ? 1 : 0;
+#pragma unroll
+            for (int j = 0; j < NL; ++j) {
+                const signed char dj = (signed char)(v & 0xff);
+                bq[((size_t)j * 32 + c) * SIL_MSTR + tid] = (unsigned char)dj;
+                v = (v - dj) >> 8;
+            }
+        }
+        __syncthreads();
+        for (;;) {
+            int l = 0;
+            if (lane == 0) l = atomicAdd(&snext[ct], 1);
+            l = blockIdx.y + gridDim.y * __builtin_amdgcn_readfirstlane(l);  // (this block's share of the labelings)
+            if (l >= L) break;
+            const int64_t lv = (int64_t)q * L + l;  // (the virtual labeling)
+            // the labeling's codes and weights: 4 consecutive positions per lane and pass
+            constexpr int NP = SIL_MT / 256;
+            int lbv[NP][4], wgv[NP][4], rwv[NP][4];
+#pragma unroll
+            for (int hh = 0; hh < NP; ++hh) {
+                const int p0 = hh * 256 + lane * 4;
+                const int4 rw = *reinterpret_cast<const int4*>(&srow[p0]);
+                const int4 cw = *reinterpret_cast<const int4*>(&scnt[p0]);
+                const int rws[4] = {rw.x, rw.y, rw.z, rw.w}, cws[4] = {cw.x, cw.y, cw.z, cw.w};
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    lbv[hh][i] = 0;
+                    wgv[hh][i] = 0;
+                    rwv[hh][i] = rws[i];
+                    if (p0 + i < nval) {
+                        if constexpr (SEG) lbv[hh][i] = sil_label(labels, m, sgs, q, l, rws[i]);
+                        else lbv[hh][i] = labels[(int64_t)l * m + rws[i]];
+                        wgv[hh][i] = rep ? cws[i] - mult[(int64_t)l * mw + rb + p0 + i] : 1;
+                    }
+                }
+            }
+            int mx = 0;
+#pragma unroll
+            for (int hh = 0; hh < NP; ++hh) {
+                const int p0 = hh * 256 + lane * 4;
+                unsigned lpk = 0, wpk = 0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int lb = lbv[hh][i], wg = wgv[hh][i];
+                    bool ok = lb >= 1 && lb <= cmax && wg > 0;
+                    if (ok && wg > 127) {  // (rare) too heavy for the int8 operand: added alone, once
+                        if (ct == 0)
+                            sil_add_row<DMAX>(x, rwv[hh][i], d, m, maxabs, wg,
+                                              gsum + (lv * (cmax + 1) + lb) * d, gsum2 + lv * (cmax + 1) + lb,
+                                              gcnt + lv * (cmax + 1) + lb);
+                        ok = false;
+                    }
+                    if (ok) {
+                        lpk |= (unsigned)lb << (8 * i);
+                        wpk |= (unsigned)wg << (8 * i);
+                        mx = max(mx, lb);
+                    }
+                }
+                *reinterpret_cast<unsigned*>(&wl[p0]) = lpk;
+                *reinterpret_cast<unsigned*>(&ww[p0]) = wpk;
+            }
+            for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o, 64));
+            __builtin_amdgcn_wave_barrier();
+            asm volatile("" ::: "memory");  // (the wave's own slice: its LDS operations are in order)
+            const int nblk = mx ? (mx >> 5) + 1 : 0;  // blocks of 32 clusters up to the largest code present
+            for (int cb = 0; cb < nblk; ++cb) {
+                sil_v16i acc[NL];
+#pragma unroll
+                for (int j = 0; j < NL; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[j][r] = 0;
+                const unsigned i4 = (unsigned)(cb * 32 + (lane & 31)) * 0x01010101u;
+                const unsigned char* bl = bq + (size_t)(lane & 31) * SIL_MSTR + h * 16;
+                for (int ks = 0; ks < nks; ++ks) {
+                    const int kb = ks * 32 + h * 16;
+                    const sil_v4i l4 = *reinterpret_cast<const sil_v4i*>(wl + kb);
+                    const sil_v4i w4 = *reinterpret_cast<const sil_v4i*>(ww + kb);
+                    sil_v4i a;
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        // bytes of l4 equal to the lane's cluster keep their weight
+                        const unsigned xo = (unsigned)l4[t] ^ i4;
+                        const unsigned nz = ((xo & 0x7f7f7f7fu) + 0x7f7f7f7fu) | xo;  // bit 7: byte != 0
+                        const unsigned eq = (~nz & 0x80808080u) >> 7;
+                        a[t] = (int)((unsigned)w4[t] & (eq * 0xffu));
+                    }
+#pragma unroll
+                    for (int j = 0; j < NL; ++j) {
+                        const sil_v4i b = *reinterpret_cast<const sil_v4i*>(bl + (size_t)j * 32 * SIL_MSTR + ks * 32);
+                        acc[j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, acc[j], 0, 0, 0);
+                    }
+                }
+                const int col = ct * 32 + (lane & 31);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int c = cb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    unsigned long long s = 0;
+#pragma unroll
+                    for (int j = 0; j < NL; ++j) s += (unsigned long long)(long long)acc[j][r] << (8 * j);
+                    if (s && c <= cmax && col < d + 2) {
+                        const int64_t lc = lv * (cmax + 1) + c;
+                        if (col < d) atomicAdd(&gsum[lc * d + col], s);
+                        else if (col == d) atomicAdd(&gsum2[lc], s);
+                        else atomicAdd(&gcnt[lc], s);
+                    }
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+            asm volatile("" ::: "memory");  // the next labeling overwrites the wave's slice
+        }
+    };
+    pass(std::integral_constant<int, 0>{});
+    if constexpr (NCT > 1) {
+        if (d + 2 > 32) {
+            __syncthreads();  // every wave is done with the first column tile
+            pass(std::integral_constant<int, 1>{});
+        }
+    }
+}
+
+// sil_sums_exc on the MFMA path: the exception rows quantised on the fly.
+template <int DMAX>
+__global__ void sil_sums_exc_x(const double* __restrict__ x, int64_t m, int d, const int32_t* __restrict__ labels,
+                               int L, int cmax, const unsigned* __restrict__ maxabs_bits,
+                               const unsigned long long* __restrict__ exc, const int* __restrict__ nexc,
+                               unsigned long long* __restrict__ gsum, unsigned long long* __restrict__ gsum2,
+                               unsigned long long* __restrict__ gcnt, SilSegs sgs) {
+    const int ne = *nexc;
+    const double maxabs = (double)__uint_as_float(*maxabs_bits);
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < ne; e += gridDim.x * blockDim.x) {
+        const int l = (int)(exc[e] >> 32);
+        const int64_t r = (int64_t)(exc[e] & 0xffffffffull);
+        const int q = sgs.nseg ? sil_seg_row(sgs.off, sgs.nseg, r) : 0;
+        const int lab = sil_label(labels, m, sgs, q, l, r);
+        if (lab < 1 || lab > cmax) continue;
+        const int64_t lc = ((int64_t)q * L + l) * (cmax + 1) + lab;
+        sil_add_row<DMAX>(x, r, d, m, maxabs, 1, gsum + lc * d, gsum2 + lc, gcnt + lc);
+    }
+}
+
+// The MFMA sums serve d <= 32 and codes that fit a byte; CCG_SIL_SUMS=scatter
+// in the environment (read per call: tools and tests run both paths in one
+// process) keeps sil_quant + sil_sums_blk, which also serve everything else.
+static bool sil_use_mfma(int d, int cmax) {
+    if (d > 32 || cmax > SIL_MCMAX) return false;
+    const char* p = getenv("CCG_SIL_SUMS");
+    return !(p && !strcmp(p, "scatter"));
 }
 
 // Dimension order of a centroid row in muc: position p holds dimension
@@ -1487,7 +1807,7 @@ static void sil_launch(const double* x, int64_t m, int d, const int32_t* labels,
                        unsigned* maxabs, unsigned long long* gsum, unsigned long long* gsum2, unsigned long long* gcnt,
                        unsigned long long* gvar, unsigned long long* wsum, unsigned long long* wcnt,
                        int* npres, int* codes, int* pos, double* mu, double* muc, double* auxc, void* q,
-                       unsigned char* img, double* out_width, int nbw, hipStream_t st, const int* rep = nullptr,
+                       bool mfma, unsigned char* img, double* out_width, int nbw, hipStream_t st, const int* rep = nullptr,
                        const int* mult = nullptr, const int* cnt = nullptr, int64_t mw = 0,
                        const unsigned long long* exc = nullptr, const int* nexc = nullptr,
                        const int64_t* nrep = nullptr, const int64_t* scan = nullptr, SilSegs sgs = SilSegs{},
@@ -1495,7 +1815,30 @@ static void sil_launch(const double* x, int64_t m, int d, const int32_t* labels,
     const bool seg = sgs.nseg > 0;
     const int Lv = seg ? sgs.nseg * L : L;  // virtual labelings
     const int T = q ? sil_tile_T(d, cmax) : 0;
-    if (T) {
+    if (mfma) {
+        // sums on the matrix core, straight from x: S1, S2 and counts in one pass, v_c in sil_mu
+        if constexpr (DMAX <= 32) {
+            const unsigned gt = (unsigned)(seg ? (int64_t)ts_tiles * (SIL_SP / SIL_MT) : ccg_cdiv(m, SIL_MT));
+            // few tiles (a small matrix): up to 8 blocks per tile share its labelings (block y takes
+            // labelings y, y + gridDim.y, ...), each staging the tile again, so that the grid still
+            // covers the CUs; from 512 tiles on (the bench's launch sets) one block per tile
+            const dim3 gb(gt, (unsigned)std::max(1, std::min(std::min(8, L), (int)(512 / gt))));
+#define SIL_MF(NL_)                                                                                                  \
+            if (seg)                                                                                                 \
+                sil_sums_mfma<DMAX, NL_, true><<<gb, SIL_MB, sil_mfma_lds(NL_), st>>>(                               \
+                    x, m, d, labels, L, cmax, maxabs, gsum, gsum2, gcnt, rep, mult, cnt, mw, nrep, scan, sgs);       \
+            else                                                                                                     \
+                sil_sums_mfma<DMAX, NL_, false><<<gb, SIL_MB, sil_mfma_lds(NL_), st>>>(                              \
+                    x, m, d, labels, L, cmax, maxabs, gsum, gsum2, gcnt, rep, mult, cnt, mw, nrep, scan, sgs)
+            if (sil_mfma_limbs(m) <= 6) { SIL_MF(6); }
+            else { SIL_MF(8); }
+#undef SIL_MF
+            if (rep)
+                sil_sums_exc_x<DMAX><<<64, 256, 0, st>>>(x, m, d, labels, L, cmax, maxabs, exc, nexc, gsum, gsum2,
+                                                         gcnt, sgs);
+            sil_mu<DMAX><<<Lv, SIL_T, 0, st>>>(m, d, cmax, maxabs, gsum, gsum2, gcnt, npres, codes, pos, mu, muc, auxc);
+        }
+    } else if (T) {
         // tiled sums: S1, S2 and counts in one pass, v_c in sil_mu
         long long* q1 = (long long*)q;
         long long* q2 = q1 + m * DMAX;
@@ -1608,8 +1951,9 @@ extern "C" int ccg_silhouette_dev(ccg_ctx* ctx, const double* x, int64_t m, int 
     int* npres = (int*)(auxc + 2 * (size_t)L * cmax);
     int* codes = npres + L;
     int* pos = codes + (size_t)L * cmax;
-    void* q = nullptr;  // fixed-point rows of the tiled sorted-segment path (cmax small enough for its LDS)
-    if (sil_tile_T(d, cmax)) {
+    const bool mfma = sil_use_mfma(d, cmax);
+    void* q = nullptr;  // fixed-point rows of the scatter sums (cmax small enough for their LDS)
+    if (!mfma && sil_tile_T(d, cmax)) {
         q = ccg_ws(ctx, WS_SIL_Q, sizeof(long long) * (size_t)m * dmax + sizeof(long long) * (size_t)m + 64);
         if (!q) return CCG_ENOMEM;
     }
@@ -1624,13 +1968,13 @@ extern "C" int ccg_silhouette_dev(ccg_ctx* ctx, const double* x, int64_t m, int 
                  st>>>(x, m * d, maxabs);
     if (d <= 16)
         sil_launch<16>(x, m, d, labels, L, cmax, maxabs, gsum, gsum2, gcnt, gvar, wsum, wcnt, npres, codes, pos, mu, muc, auxc, q,
-                        img, out_width, nbw, st);
+                        mfma, img, out_width, nbw, st);
     else if (d <= 32)
         sil_launch<32>(x, m, d, labels, L, cmax, maxabs, gsum, gsum2, gcnt, gvar, wsum, wcnt, npres, codes, pos, mu, muc, auxc, q,
-                        img, out_width, nbw, st);
+                        mfma, img, out_width, nbw, st);
     else
         sil_launch<64>(x, m, d, labels, L, cmax, maxabs, gsum, gsum2, gcnt, gvar, wsum, wcnt, npres, codes, pos, mu, muc, auxc, q,
-                        img, out_width, nbw, st);
+                        mfma, img, out_width, nbw, st);
     sil_final<<<L, 256, 0, st>>>(m, L, cmax, nbw, gcnt, wsum, wcnt, out_mean, out_nclust, out_minsize, SilSegs{});
     ccg_timer_stop(ctx, t_all, st);
     CCG_HIP(hipGetLastError());
@@ -1665,8 +2009,9 @@ static int sil_cells_run(ccg_ctx* ctx, const double* x, int64_t m, int d, const 
     int* npres = (int*)(auxc + 2 * (size_t)Lv * cmax);
     int* codes = npres + Lv;
     int* pos = codes + (size_t)Lv * cmax;
-    void* q = nullptr;  // fixed-point rows of the tiled sums (cmax small enough for its LDS)
-    if (sil_tile_T(d, cmax)) {
+    const bool mfma = sil_use_mfma(d, cmax);
+    void* q = nullptr;  // fixed-point rows of the scatter sums (cmax small enough for their LDS)
+    if (!mfma && sil_tile_T(d, cmax)) {
         q = ccg_ws(ctx, WS_SIL_Q, sizeof(long long) * (size_t)m * dmax + sizeof(long long) * (size_t)m + 64);
         if (!q) return CCG_ENOMEM;
     }
@@ -1710,7 +2055,7 @@ static int sil_cells_run(ccg_ctx* ctx, const double* x, int64_t m, int d, const 
                  st>>>(x, m * d, maxabs);
 #define SIL_CELLS(DM_)                                                                                              \
     sil_launch<DM_>(x, m, d, labels, L, cmax, maxabs, gsum, gsum2, gcnt, gvar, wsum, wcnt, npres, codes, pos, mu, muc, \
-                    auxc, q, img, nullptr, nbw, st, rep, mult, cnt, m, exc, nexc, scan + m, scan, sgs, ts_tiles,     \
+                    auxc, q, mfma, img, nullptr, nbw, st, rep, mult, cnt, m, exc, nexc, scan + m, scan, sgs, ts_tiles,     \
                     tw_tiles)
     if (d <= 16) SIL_CELLS(16);
     else if (d <= 32) SIL_CELLS(32);

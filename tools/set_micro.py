@@ -3,7 +3,12 @@ nb bootstraps (default 8) of bench.py's synthetic PCs through
 ccg_knn_boots_table_dev, one class-level SNN pass over the batch and one
 ccg_silhouette_segments_dev, each stage timed in isolation by the library's
 hipEvent timers (ms per bootstrap), plus digests of the outputs so variant
-builds (--lib, tools/build_variant.sh) can be checked for equal results."""
+builds (--lib, tools/build_variant.sh) can be checked for equal results.
+digest_sil_toggle_unset / _scatter: a hash of the silhouette outputs of one
+more call each with CCG_SIL_SUMS unset (the library's default sums path) and
+set to "scatter"; SM_SIL_DIGESTS=0 in the environment skips those two calls,
+so that a profiler run sees only the timed launch sets."""
+import hashlib
 import json
 import os
 import sys
@@ -72,6 +77,30 @@ def main():
     out["digest_snn"] = [int(x) for x in info.tolist()] + [int(sb.nbr[:used].to(torch.int64).sum().item()),
                                                             int(sb.wpk[:used].to(torch.int64).sum().item())]
     out["digest_sil"] = float(means.sum().item())
+
+    # the silhouette outputs bit for bit, with CCG_SIL_SUMS unset (the sums on
+    # the matrix core where the library has them) and set to "scatter" (the
+    # library reads it per call)
+    def sil_digest(toggle):
+        old = os.environ.pop("CCG_SIL_SUMS", None)
+        if toggle:
+            os.environ["CCG_SIL_SUMS"] = toggle
+        try:
+            eng.silhouette_segments_t(rows, off, [labels[j] for j in range(nb)], cmax, keys, nb * N,
+                                      [means[j] for j in range(nb)], [nclust[j] for j in range(nb)],
+                                      [minsize[j] for j in range(nb)])
+            torch.cuda.synchronize()
+        finally:
+            os.environ.pop("CCG_SIL_SUMS", None)
+            if old is not None:
+                os.environ["CCG_SIL_SUMS"] = old
+        h = hashlib.sha256()
+        for t in (means, nclust, minsize):
+            h.update(t.cpu().numpy().tobytes())
+        return h.hexdigest()[:16]
+    if os.environ.get("SM_SIL_DIGESTS", "1") != "0":
+        out["digest_sil_toggle_unset"] = sil_digest(None)
+        out["digest_sil_toggle_scatter"] = sil_digest("scatter")
     print(json.dumps(out))
 
 

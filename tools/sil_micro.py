@@ -3,6 +3,7 @@ shapes: one 90k-row bootstrap of bench.py's synthetic PCs (d = 30) and 60
 synthetic clusterings (bench.synth_labels, drawn per cell).  Reports ms per
 call (library hipEvent timer) of the row path (ccg_silhouette_dev) and of the
 distinct-cell path (ccg_silhouette_cells_dev).  --lib selects a variant build (tools/build_variant.sh)."""
+import hashlib
 import json
 import os
 import sys
@@ -47,9 +48,35 @@ def main():
     for _ in range(reps):
         eng.silhouette_cells_t(rows, labels, cmax, boot, N, mean, ncl, mns)
     ms_c, cnt_c = eng.timing_read("silhouette")
-    print(json.dumps({"lib": os.path.basename(_lib.LIB_PATH), "sil_ms": ms / cnt, "sil_cells_ms": ms_c / cnt_c,
-                      "cmax": cmax, "mean0": float(mean_rows[0].item()),
-                      "max_abs_diff_cells": float((mean - mean_rows).abs().max().item())}))
+    out = {"lib": os.path.basename(_lib.LIB_PATH), "sil_ms": ms / cnt, "sil_cells_ms": ms_c / cnt_c,
+           "cmax": cmax, "mean0": float(mean_rows[0].item()),
+           "max_abs_diff_cells": float((mean - mean_rows).abs().max().item())}
+
+    # both forms' outputs bit for bit, with the sums on the matrix core
+    # (CCG_SIL_SUMS unset) and with the scatter sums (CCG_SIL_SUMS=scatter,
+    # read by the library per call)
+    def digest(toggle, cells):
+        old = os.environ.pop("CCG_SIL_SUMS", None)
+        if toggle:
+            os.environ["CCG_SIL_SUMS"] = toggle
+        try:
+            if cells:
+                eng.silhouette_cells_t(rows, labels, cmax, boot, N, mean, ncl, mns)
+            else:
+                eng.silhouette_t(rows, labels, cmax, mean, ncl, mns)
+            torch.cuda.synchronize()
+        finally:
+            os.environ.pop("CCG_SIL_SUMS", None)
+            if old is not None:
+                os.environ["CCG_SIL_SUMS"] = old
+        h = hashlib.sha256()
+        for t in (mean, ncl, mns):
+            h.update(t.cpu().numpy().tobytes())
+        return h.hexdigest()[:16]
+    for cells in (False, True):
+        for toggle in (None, "scatter"):
+            out["digest_%s_%s" % ("cells" if cells else "rows", "toggle_" + (toggle or "unset"))] = digest(toggle, cells)
+    print(json.dumps(out))
 
 
 if __name__ == "__main__":
