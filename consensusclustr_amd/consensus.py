@@ -120,7 +120,7 @@ def mapback(boot_idx, labels_boot, N):
 # ------------------------------------------------------- bootstrap path --
 def getClustAssignments(pca, boot_idx=None, clusterFun="leiden", resRange=RES_RANGE, kNum=K_NUM,
                         mode="robust", cellOrder=None, seed=123, minSize=0, engine=None,
-                        return_details=False, knn=None):
+                        return_details=False, knn=None, snn_emit="host"):
     """Mirror of getClustAssignments (R/consensusClust.R:650-692).
 
     pca: N x d PC matrix of all cells; the clustered matrix is pca[boot_idx]
@@ -129,7 +129,8 @@ def getClustAssignments(pca, boot_idx=None, clusterFun="leiden", resRange=RES_RA
     cellOrder: only the identity order of pca's rows is supported (the
     reference always passes rownames(pca)).  knn: this bootstrap's n x kmax
     neighbour rows when the caller already searched them in a batch
-    (consensus_cluster); None searches here.
+    (consensus_cluster); None searches here.  snn_emit: where the kNum graphs'
+    edge lists are formed, "host" or "device" (Engine.snn_multi's emit).
     Returns length-N int32 labels (robust) or N x (|kNum|*|resRange|) (granular),
     -1 for cells not in the bootstrap.
     """
@@ -148,7 +149,7 @@ def getClustAssignments(pca, boot_idx=None, clusterFun="leiden", resRange=RES_RA
         raise ValueError(f"knn must be {n} x {kmax}, got {knn.shape}")
     fn = _cluster_fn(clusterFun)
     # every k in one pass (:656-658); copies of a cell share a row class
-    graphs = eng.snn_multi(knn, [int(k) for k in kNum], "number", cell=boot_idx)
+    graphs = eng.snn_multi(knn, [int(k) for k in kNum], "number", cell=boot_idx, emit=snn_emit)
     jobs = [(n, *graphs[g], float(res), seed) for g in range(len(kNum)) for res in resRange]  # :653-654, k outer
     lab = np.stack([np.asarray(x, np.int32) for x in _cluster_all(fn, jobs)])
     if mode == "robust":
@@ -216,7 +217,7 @@ def bootstrap_knn_batches(pca, boots, kmax, engine=None, group=None, batch=32):
 
 def consensus_cluster(pca, nboots=100, bootSize=0.9, clusterFun="leiden", resRange=RES_RANGE, kNum=K_NUM,
                       mode="robust", seed=123, engine=None, boot_indices=None, return_matrix=None,
-                      merge=False, minStability=0.175, group=None, boot_seed=None, boot_knn=None):
+                      merge=False, minStability=0.175, group=None, boot_seed=None, boot_knn=None, snn_emit="host"):
     """The bootstrap + consensus core of consensusClust (R/consensusClust.R:388-456).
 
     The bootstrap loop runs as the R drop-in does (R/ccg.R ccgConsensusCore):
@@ -229,6 +230,7 @@ def consensus_cluster(pca, nboots=100, bootSize=0.9, clusterFun="leiden", resRan
     reference -- iterate=TRUE forwards BPPARAM but not seed (:562-566).
     boot_knn: (nboots, n, max(kNum)) neighbour rows of every bootstrap when a
     caller already searched them (the level-batched iterate driver).
+    snn_emit: "host" or "device", handed to every bootstrap's getClustAssignments.
     Returns dict(assignments=<chosen consensus labels>, clustAssignments=<B x N
     uint8/uint16>, scores=<consensus scores>, choice=<index>, candidates,
     consensus_knn=<N x max(kNum)>) and, when return_matrix (default: N <=
@@ -255,7 +257,7 @@ def consensus_cluster(pca, nboots=100, bootSize=0.9, clusterFun="leiden", resRan
             try:
                 columns.append(getClustAssignments(pca, boots[b], clusterFun=fn, resRange=resRange, kNum=kNum,
                                                    mode=mode, seed=seed, engine=eng,
-                                                   knn=None if knn is None else knn[b - b0]))
+                                                   knn=None if knn is None else knn[b - b0], snn_emit=snn_emit))
             except Exception:  # tryCatch(..., error = rep(1, N)), :397-399
                 columns.append(np.ones(N, np.int32))
     A = assignment_matrix(columns)
@@ -450,10 +452,11 @@ NULL_RES_RANGE = np.concatenate([np.arange(0.01, 0.3 + 1e-12, 0.03), np.arange(0
 
 
 def null_statistics(pca_nulls, kNum=K_NUM, clusterFun="leiden", resRange=NULL_RES_RANGE, minSize=5, seed=123,
-                    engine=None):
+                    engine=None, snn_emit="host"):
     """generateNullStatistic (:796-813) for every null PC matrix: the mean
     approxSilhouette of getClustAssignments(pcaNull, robust, minSize=5), 0 if
-    the PCA failed (None / all NaN) or one cluster was chosen."""
+    the PCA failed (None / all NaN) or one cluster was chosen.  snn_emit: "host"
+    or "device" (Engine.snn_multi's emit)."""
     eng = engine or default_engine()
     fn = _cluster_fn(clusterFun)
     kmax = max(kNum)
@@ -466,7 +469,7 @@ def null_statistics(pca_nulls, kNum=K_NUM, clusterFun="leiden", resRange=NULL_RE
     for t, X, (knn, _) in zip(ok, mats, knns):
         n = X.shape[0]
         labels = []
-        graphs = eng.snn_multi(np.ascontiguousarray(knn), [int(k) for k in kNum], "number")
+        graphs = eng.snn_multi(np.ascontiguousarray(knn), [int(k) for k in kNum], "number", emit=snn_emit)
         for g, k in enumerate(kNum):  # getClustAssignments' k-outer / resolution-inner loop (:653-654)
             ei, ej, w = graphs[g]
             for res in resRange:

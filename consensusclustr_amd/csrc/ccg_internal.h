@@ -65,6 +65,8 @@ enum ccg_ws_slot {
     WS_SIL_SEG,      // silhouette segments: offsets, tile starts, label and output pointers
     WS_FX_C,         // kNN segmented exact search: the compacted failed list, radii, segment offsets
     WS_KBT,          // kNN bootstrap batches: segment offsets (distinct cells, rows), per-segment fail counts
+    WS_SNN_EXP,      // SNN class expansion: class maps, member lists, per-row counts / cursors / offsets, long rows
+    WS_SNN_EDGES,    // SNN per-graph edge lists staged on the device (ccg_snn_edges_stage / _fetch)
     WS_NSLOTS
 };
 

@@ -1027,7 +1027,8 @@ __global__ __launch_bounds__(256) void snn_copy_rows_kernel(int64_t n, SnnSpec s
 // checks the prefix property on every root's list (an input that breaks it
 // sets the status: the caller takes the row-level pass).  At cfg3 a root has
 // ~14 member classes instead of 21 member rows, and the class items are ~1/3
-// of the row items; the rows are expanded only on the host (ccg_snn_graphs).
+// of the row items; the rows are expanded on the host (ccg_snn_graphs) or, on
+// request, on the device (ccg_snn_edges_cells_dev, below).
 
 // root[x]: the end of x's src chain (src[r] < r); isroot[x] for the scan that
 // numbers the classes (ordinal = exclusive prefix at the root).
@@ -1618,10 +1619,13 @@ static bool snn_cls_ok(const SnnSpec& sp) { return sp.type == CCG_SNN_NUMBER && 
 // roff[n] <= cap.  *cnt_out: per-graph exclusive scans of the class rows'
 // edge counts; *u_out: device u; *status_out: device int, nonzero when the
 // input breaks the class contract (a prefix check failed: take the row pass).
+// *crank_out / *csize_out (optional): every row's rank among its class's rows
+// and every class's size over ordinals (valid until the next build).
 static int snn_build_cls(ccg_ctx* ctx, const int32_t* knn, int64_t n, int kstride, const int32_t* cell,
                          const SnnSpec& sp, hipStream_t st, int32_t* row_class, int32_t* croot, int64_t* roff,
                          int32_t* rlen, int32_t* nbr, uint32_t* wpk, int64_t cap, int64_t** cnt_out,
-                         const int64_t** u_out, const int** status_out) {
+                         const int64_t** u_out, const int** status_out, const int** crank_out = nullptr,
+                         const int** csize_out = nullptr) {
     const int kmax = sp.kk[sp.nk - 1];
     const int64_t S = n * (kmax + 1);  // member slots (root row, rank)
     CCG_REQUIRE(S < (1LL << 31) - 64, "SNN: n*(kmax+1) too large");
@@ -1720,6 +1724,8 @@ static int snn_build_cls(ccg_ctx* ctx, const int32_t* knn, int64_t n, int kstrid
     *cnt_out = cnt;
     *u_out = ucount;
     *status_out = status;
+    if (crank_out) *crank_out = crank;
+    if (csize_out) *csize_out = csize;
     CCG_HIP(hipGetLastError());
     return CCG_OK;
 }
@@ -1835,6 +1841,425 @@ extern "C" int ccg_snn_reserve(ccg_ctx* ctx, int64_t entries) {
     return CCG_OK;
 }
 
+// ------------------------------------- class rows -> row-level edge lists --
+// The device expansion of the class graph (ccg_snn_edges_cells_dev): what
+// snn_stage_classes + the class branch of ccg_snn_graph_fetch do on host
+// threads.  For graph t, row x of class C gets every row y > x of C (weight
+// ks[t] + 1) and every row y > x of each class H whose byte t with C is
+// non-zero (that byte), sorted by y.  A class row stores partners H > C only,
+// but the member rows of C and H interleave, so every class edge (C, H) hands
+// each pair (x in C, y in H) to row min(x, y).
+//   1. member lists: a scan of the class sizes over ordinals, then
+//      mrows[ms[c] + crank[x]] = x (ascending within a class, no sort).
+//   2. count: one wave per class walks its row; int32 atomicAdd on the
+//      per-(graph, row) counters (integer totals do not depend on the order).
+//      Lengths = counts + the rows above x in its own class; ONE scan of the
+//      graphs' lengths laid end to end (as snn_emit_kernel's off).
+//   3. fill: the same walk scatters keys (y << 8 | w) into the row's segment of
+//      out_j (n < 2^21 for the class build, w <= 33: 29 bits).  The in-class
+//      part has fixed slots; the rest takes slots from the counter, in any
+//      order.
+//   4. sort: every row's segment is sorted in place (the y of one row are
+//      distinct, so the result does not depend on the fill order) and written
+//      as (i, j, w).  Rows of at most SNN_EXP_WAVE_MAX entries: one wave, the
+//      register bitonic network of the build tiers (64 E keys, E = 4 / 16 /
+//      32), transposed through LDS for coalesced stores.  Longer rows: one
+//      block and an n-entry table in global memory (the dense tier's scratch):
+//      w is stored at its y, then the table is compacted in y order -- O(n) per
+//      row, exact for every n, no LDS-tied bound.
+#define SNN_EXP_WAVE_MAX 2048  // entries of the longest row the register tier sorts
+#define SNN_EXP_F_GO 0         // flags: the class rows are valid and were written
+#define SNN_EXP_F_WR 1         //        [1 .. 4] graph t is written
+#define SNN_EXP_F_NLONG 5      //        rows beyond the register tier
+#define SNN_EXP_NFLAGS 16
+
+struct SnnExp {
+    int64_t* ms;     // [n + 1] member-list offsets over class ordinals (ms[u..] = n)
+    int32_t* mrows;  // [n] rows of every class, ascending
+    int32_t* cur;    // [nk n] per-(graph, row) cross-class counts, then fill cursors
+    int64_t* off;    // [nk (n + 1) + 1] lengths -> one exclusive scan over all graphs
+    int32_t* longl;  // [nk n] (t n + x) of the rows beyond the register tier
+    int32_t* flags;  // [SNN_EXP_NFLAGS]
+};
+
+// Class sizes over ordinals for the member-list scan; zeroes the counters.
+__global__ void snn_exp_init_kernel(int64_t n, int nk, const int64_t* __restrict__ ucount,
+                                    const int* __restrict__ status, const int64_t* __restrict__ roff, int64_t rcap,
+                                    const int* __restrict__ csize, SnnExp ex) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c == 0) {
+        ex.flags[SNN_EXP_F_GO] = (*status == 0 && roff[n] <= rcap) ? 1 : 0;
+        ex.flags[SNN_EXP_F_NLONG] = 0;
+    }
+    if (c > n) return;
+    ex.ms[c] = c < *ucount ? csize[c] : 0;
+    if (c < n)
+        for (int t = 0; t < nk; ++t) ex.cur[(int64_t)t * n + c] = 0;
+}
+
+__global__ void snn_exp_members_kernel(int64_t n, const int* __restrict__ row_class, const int* __restrict__ crank,
+                                       SnnExp ex) {
+    const int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= n) return;
+    const int c = row_class[x];
+    if ((unsigned)c >= (unsigned)n) return;
+    const int64_t p = ex.ms[c] + crank[x];
+    if (p >= 0 && p < n) ex.mrows[p] = (int32_t)x;  // (a valid kNN fills every slot once)
+}
+
+// The walk over the class rows: one wave per class C, one lane per entry
+// (C, H); every pair (x in C, y in H) of a graph holding the entry goes to
+// row min(x, y).  FILL = false counts; FILL = true writes the keys -- first
+// the in-class part of every row of C at its fixed slots.
+template <bool FILL>
+__global__ __launch_bounds__(256) void snn_exp_pairs_kernel(int64_t n, SnnSpec sp, const int64_t* __restrict__ ucount,
+                                                            SnnRows rows, SnnExp ex, SnnOut out) {
+    if (!ex.flags[SNN_EXP_F_GO]) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t u = *ucount;
+    bool wr[SNN_MAXK];
+    int64_t g0[SNN_MAXK];
+#pragma unroll
+    for (int t = 0; t < SNN_MAXK; ++t) {
+        wr[t] = t < sp.nk && (!FILL || ex.flags[SNN_EXP_F_WR + t] != 0);
+        g0[t] = (FILL && t < sp.nk) ? ex.off[(int64_t)t * (n + 1)] : 0;
+    }
+    for (int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); c < u; c += (int64_t)gridDim.x * 4) {
+        const int64_t cb = ex.ms[c];
+        const int64_t mc = ex.ms[c + 1] - cb;
+        if (cb < 0 || mc < 0 || cb + mc > n) continue;  // (invalid input only)
+        if (FILL) {
+            for (int64_t p = lane; p < mc * mc; p += 64) {
+                const int64_t a = p / mc, b = p - a * mc;
+                if (b <= a) continue;
+                const int x = ex.mrows[cb + a], y = ex.mrows[cb + b];
+                if ((unsigned)x >= (unsigned)n || (unsigned)y >= (unsigned)n) continue;
+#pragma unroll
+                for (int t = 0; t < SNN_MAXK; ++t) {
+                    if (!wr[t]) continue;
+                    const int64_t pos = ex.off[(int64_t)t * (n + 1) + x] - g0[t] + (b - a - 1);
+                    if (pos >= 0 && pos < out.cap[t]) out.oj[t][pos] = (int32_t)(((unsigned)y << 8) | (unsigned)(sp.kk[t] + 1));
+                }
+            }
+        }
+        const int64_t ro = rows.roff[c];
+        const int len = rows.rlen[c];
+        for (int r = lane; r < len; r += 64) {
+            const unsigned v = rows.wpk[ro + r];
+            const int h = rows.nbr[ro + r];
+            if (v == 0u || h < 0 || h >= u) continue;
+            const int64_t hb = ex.ms[h];
+            const int64_t mh = ex.ms[h + 1] - hb;
+            if (hb < 0 || mh < 0 || hb + mh > n) continue;
+            for (int64_t a = 0; a < mc; ++a) {
+                const int x = ex.mrows[cb + a];
+                if ((unsigned)x >= (unsigned)n) continue;
+                for (int64_t b = 0; b < mh; ++b) {
+                    const int y = ex.mrows[hb + b];
+                    if ((unsigned)y >= (unsigned)n) continue;
+                    const int i = x < y ? x : y, j = x < y ? y : x;
+#pragma unroll
+                    for (int t = 0; t < SNN_MAXK; ++t) {
+                        const unsigned w = (v >> (8 * t)) & 0xFFu;
+                        if (!wr[t] || w == 0u) continue;
+                        const int q = atomicAdd(&ex.cur[(int64_t)t * n + i], 1);
+                        if (FILL) {
+                            const int64_t pos = ex.off[(int64_t)t * (n + 1) + i] - g0[t] + q;
+                            if (pos >= 0 && pos < out.cap[t])  // (q stays below the counted length)
+                                out.oj[t][pos] = (int32_t)(((unsigned)j << 8) | w);
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
+// Length of every (graph, row): the cross-class count plus the rows above x
+// in its own class; the counter becomes the fill cursor past the in-class
+// part; rows beyond the register tier are listed (in any order: each sorts
+// its own segment).
+__global__ void snn_exp_len_kernel(int64_t n, int nk, const int* __restrict__ row_class,
+                                   const int* __restrict__ crank, SnnExp ex) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (int64_t)nk * (n + 1)) return;
+    const int t = (int)(idx / (n + 1));
+    const int64_t x = idx - (int64_t)t * (n + 1);
+    if (x == n) {
+        ex.off[idx] = 0;
+        return;
+    }
+    int64_t in = 0, cross = 0;
+    if (ex.flags[SNN_EXP_F_GO]) {
+        const int c = row_class[x];
+        if ((unsigned)c < (unsigned)n) in = ex.ms[c + 1] - ex.ms[c] - 1 - crank[x];
+        if (in < 0 || in > n) in = 0;  // (invalid input only)
+        cross = ex.cur[(int64_t)t * n + x];
+    }
+    const int64_t len = in + cross;
+    ex.off[idx] = len;
+    ex.cur[(int64_t)t * n + x] = (int32_t)in;
+    if (len > SNN_EXP_WAVE_MAX) ex.longl[atomicAdd(&ex.flags[SNN_EXP_F_NLONG], 1)] = (int32_t)((int64_t)t * n + x);
+}
+
+// d_info of ccg_snn_edges_cells_dev and the per-graph write flags.
+__global__ void snn_exp_info_kernel(int64_t n, int nk, const int64_t* __restrict__ ucount,
+                                    const int* __restrict__ status, const int64_t* __restrict__ roff, int64_t rcap,
+                                    SnnExp ex, SnnOut out, int64_t* __restrict__ info) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const bool fit = roff[n] <= rcap;
+    const bool ok = *status == 0;
+    info[0] = *ucount;
+    info[1] = *status;
+    info[2] = roff[n];
+    for (int t = 0; t < SNN_MAXK; ++t) {
+        if (t >= nk) {
+            ex.flags[SNN_EXP_F_WR + t] = 0;
+            continue;
+        }
+        const int64_t e = ex.off[(int64_t)t * (n + 1) + n] - ex.off[(int64_t)t * (n + 1)];
+        info[3 + t] = !fit ? -roff[n] : (ok ? e : 0);
+        ex.flags[SNN_EXP_F_WR + t] = (fit && ok && out.cap[t] > 0 && e <= out.cap[t]) ? 1 : 0;
+    }
+}
+
+// One row's segment (at most 64 E keys, in out_j) sorted by one wave and
+// written as (i, j, w).  The bitonic network takes the keys in any order, so
+// they are loaded element-major (coalesced); it leaves them lane-major, and
+// the LDS transpose (padded one word per 32) makes the stores coalesced too.
+template <int E>
+__device__ __forceinline__ void snn_exp_sort_row(uint32_t* lds, int32_t* oi, int32_t* oj, double* ow, int64_t base,
+                                                 int len, int x, int lane) {
+    uint32_t k[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) k[e] = 64 * e + lane < len ? (uint32_t)oj[base + 64 * e + lane] : ~0u;
+    snn_bitonic<E, uint32_t>(k, lane);
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int i = E * lane + e;
+        lds[i + (i >> 5)] = k[e];
+    }
+    WAVE_LDS_SYNC();
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int i = 64 * e + lane;
+        if (i < len) {
+            const uint32_t v = lds[i + (i >> 5)];
+            oi[base + i] = x;
+            oj[base + i] = (int32_t)(v >> 8);
+            ow[base + i] = (double)(v & 0xFFu);
+        }
+    }
+    WAVE_LDS_SYNC();
+}
+
+__global__ __launch_bounds__(256) void snn_exp_sort_kernel(int64_t n, int nk, SnnExp ex, SnnOut out) {
+    __shared__ uint32_t lds[4][SNN_EXP_WAVE_MAX + SNN_EXP_WAVE_MAX / 32];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t tasks = (int64_t)nk * n;
+    for (int64_t q = (int64_t)blockIdx.x * 4 + wv; q < tasks; q += (int64_t)gridDim.x * 4) {
+        const int t = (int)(q / n);
+        const int64_t x = q - (int64_t)t * n;
+        if (!ex.flags[SNN_EXP_F_WR + t]) continue;
+        const int64_t e0 = ex.off[(int64_t)t * (n + 1) + x];
+        const int64_t l64 = ex.off[(int64_t)t * (n + 1) + x + 1] - e0;
+        if (l64 <= 0 || l64 > SNN_EXP_WAVE_MAX) continue;  // long rows: snn_exp_long_kernel
+        const int64_t base = e0 - ex.off[(int64_t)t * (n + 1)];
+        if (base + l64 > out.cap[t]) continue;  // (never for a written graph)
+        const int len = (int)l64;
+        if (len <= 256) snn_exp_sort_row<4>(lds[wv], out.oi[t], out.oj[t], out.ow[t], base, len, (int)x, lane);
+        else if (len <= 1024) snn_exp_sort_row<16>(lds[wv], out.oi[t], out.oj[t], out.ow[t], base, len, (int)x, lane);
+        else snn_exp_sort_row<32>(lds[wv], out.oi[t], out.oj[t], out.ow[t], base, len, (int)x, lane);
+    }
+}
+
+// Rows beyond the register tier: one block per row and its n-entry table tab
+// (w at y; the y of a row are distinct and above x), compacted in y order.
+__global__ __launch_bounds__(256) void snn_exp_long_kernel(int64_t n, SnnExp ex, SnnOut out,
+                                                           unsigned* __restrict__ dense) {
+    __shared__ int wsum[4];
+    unsigned* tab = dense + (int64_t)blockIdx.x * n;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int nlong = ex.flags[SNN_EXP_F_NLONG];
+    for (int q = blockIdx.x; q < nlong; q += gridDim.x) {
+        const int64_t id = ex.longl[q];
+        const int t = (int)(id / n);
+        const int64_t x = id - (int64_t)t * n;
+        if (t < 0 || t >= SNN_MAXK || !ex.flags[SNN_EXP_F_WR + t]) continue;
+        const int64_t e0 = ex.off[(int64_t)t * (n + 1) + x];
+        const int64_t len = ex.off[(int64_t)t * (n + 1) + x + 1] - e0;
+        const int64_t base = e0 - ex.off[(int64_t)t * (n + 1)];
+        if (base < 0 || base + len > out.cap[t]) continue;  // (never for a written graph)
+        int32_t* oi = out.oi[t];
+        int32_t* oj = out.oj[t];
+        double* ow = out.ow[t];
+        for (int64_t y = x + 1 + threadIdx.x; y < n; y += 256) tab[y] = 0u;
+        __syncthreads();
+        for (int64_t i = threadIdx.x; i < len; i += 256) {
+            const uint32_t k = (uint32_t)oj[base + i];
+            const int64_t y = k >> 8;
+            if (y > x && y < n) tab[y] = k & 0xFFu;
+        }
+        __syncthreads();
+        int64_t pos = base;
+        for (int64_t y0 = x + 1; y0 < n; y0 += 256) {
+            const int64_t y = y0 + threadIdx.x;
+            const unsigned w = y < n ? tab[y] : 0u;
+            const unsigned long long m = __ballot(w != 0u);
+            if (lane == 0) wsum[wv] = __popcll(m);
+            __syncthreads();
+            int before = 0, tot = 0;
+            for (int v = 0; v < 4; ++v) {
+                before += v < wv ? wsum[v] : 0;
+                tot += wsum[v];
+            }
+            if (w != 0u) {
+                const int64_t p = pos + before + __popcll(m & lanemask_lt());
+                if (p < base + len) {
+                    oi[p] = (int32_t)x;
+                    oj[p] = (int32_t)y;
+                    ow[p] = (double)w;
+                }
+            }
+            pos += tot;
+            __syncthreads();
+        }
+    }
+}
+
+static int snn_out_spec(const char* who, int nk, int32_t* const* out_i, int32_t* const* out_j, double* const* out_w,
+                        const int64_t* caps, SnnOut* out) {
+    for (int t = 0; t < SNN_MAXK; ++t) {
+        out->cap[t] = 0;
+        out->oi[t] = nullptr;
+        out->oj[t] = nullptr;
+        out->ow[t] = nullptr;
+    }
+    for (int t = 0; t < nk; ++t) {
+        out->cap[t] = caps ? caps[t] : 0;
+        CCG_REQUIRE(out->cap[t] >= 0, "%s: negative capacity", who);
+        if (out->cap[t] > 0) {
+            CCG_REQUIRE(out_i && out_j && out_w && out_i[t] && out_j[t] && out_w[t], "%s: NULL outputs with cap > 0",
+                        who);
+            out->oi[t] = out_i[t];
+            out->oj[t] = out_j[t];
+            out->ow[t] = out_w[t];
+        }
+    }
+    return CCG_OK;
+}
+
+// What the count phase leaves in the workspaces for the emission.
+struct SnnExpRun {
+    SnnExp ex;
+    SnnRows rows;
+    const int64_t* u;
+    const int* status;
+    unsigned* dense;
+};
+
+// The class pass into the context's row reservation and the count phase of
+// the expansion: every (graph, row)'s length and offset.  No host sync.
+static int snn_edges_count(ccg_ctx* ctx, const int32_t* knn, int64_t n, int kstride, const int32_t* cell,
+                           const SnnSpec& sp, SnnExpRun* R, hipStream_t st) {
+    const int nk = sp.nk, kmax = sp.kk[nk - 1];
+    CCG_REQUIRE(n < (1LL << SNN_CLS_BITS), "SNN: n must be below 2^%d", SNN_CLS_BITS);
+    // every workspace before the first launch: growth discards a slot's contents
+    const size_t b_ms = sizeof(int64_t) * (n + 1), b_off = sizeof(int64_t) * ((size_t)nk * (n + 1) + 1);
+    const size_t b_roff = sizeof(int64_t) * (n + 1);
+    const size_t b_n = sizeof(int32_t) * n, b_nk = sizeof(int32_t) * (size_t)nk * n;
+    char* eb = (char*)ccg_ws(ctx, WS_SNN_EXP,
+                             b_ms + b_off + b_roff + 3 * b_n + 2 * b_nk + sizeof(int32_t) * (n + 64 + SNN_EXP_NFLAGS));
+    const int64_t rcap =
+        ctx->snn_row_reserve > 0 ? ctx->snn_row_reserve : (int64_t)SNN_ROW_RESERVE * n * (kmax + 1);
+    char* rbuf = (char*)ccg_ws(ctx, WS_SNN_ROWS, (sizeof(int32_t) + sizeof(uint32_t)) * rcap + sizeof(int32_t) * (n + 64));
+    if (!eb || !rbuf) return CCG_ENOMEM;
+    SnnExp ex;
+    ex.ms = (int64_t*)eb;
+    ex.off = (int64_t*)(eb + b_ms);
+    int64_t* roff = (int64_t*)(eb + b_ms + b_off);
+    ex.mrows = (int32_t*)(eb + b_ms + b_off + b_roff);
+    int32_t* row_class = ex.mrows + n;
+    int32_t* croot = row_class + n;
+    ex.cur = croot + n;
+    ex.longl = ex.cur + (int64_t)nk * n;
+    ex.flags = ex.longl + (int64_t)nk * n;
+    int32_t* nbr = (int32_t*)rbuf;
+    uint32_t* wpk = (uint32_t*)(nbr + rcap);
+    int32_t* rlen = (int32_t*)(wpk + rcap);
+    int64_t* cnt = nullptr;
+    const int64_t* u = nullptr;
+    const int* status = nullptr;
+    const int* crank = nullptr;
+    const int* csize = nullptr;
+    int rc = snn_build_cls(ctx, knn, n, kstride, cell, sp, st, row_class, croot, roff, rlen, nbr, wpk, rcap, &cnt, &u,
+                           &status, &crank, &csize);
+    if (rc) return rc;
+    unsigned* dense = (unsigned*)ccg_ws(ctx, WS_SNN_D, sizeof(unsigned) * n * SNN_DENSE_BLOCKS);  // (the build's: no growth)
+    if (!dense) return CCG_ENOMEM;
+    const SnnRows rows{roff, rlen, nbr, wpk, rcap};
+    const unsigned gw = (unsigned)std::min<int64_t>(ccg_cdiv(n, 4), 16384);
+    snn_exp_init_kernel<<<(unsigned)ccg_cdiv(n + 1, 256), 256, 0, st>>>(n, nk, u, status, roff, rcap, csize, ex);
+    rc = ccg_scan_i64(ctx, ex.ms, ex.ms, n, st);
+    if (rc) return rc;
+    snn_exp_members_kernel<<<(unsigned)ccg_cdiv(n, 256), 256, 0, st>>>(n, row_class, crank, ex);
+    snn_exp_pairs_kernel<false><<<gw, 256, 0, st>>>(n, sp, u, rows, ex, SnnOut{});
+    snn_exp_len_kernel<<<(unsigned)ccg_cdiv((int64_t)nk * (n + 1), 256), 256, 0, st>>>(n, nk, row_class, crank, ex);
+    rc = ccg_scan_i64(ctx, ex.off, ex.off, (int64_t)nk * (n + 1), st);
+    if (rc) return rc;
+    *R = SnnExpRun{ex, rows, u, status, dense};
+    CCG_HIP(hipGetLastError());
+    return CCG_OK;
+}
+
+// d_info and, for the graphs that fit their capacity, the fill and the sorts
+// (once per count phase: the fill consumes the cursors).
+static int snn_edges_emit(int64_t n, const SnnSpec& sp, const SnnExpRun& R, const SnnOut& out, int64_t* d_info,
+                          hipStream_t st) {
+    const int nk = sp.nk;
+    snn_exp_info_kernel<<<1, 64, 0, st>>>(n, nk, R.u, R.status, R.rows.roff, R.rows.cap, R.ex, out, d_info);
+    bool any_cap = false;
+    for (int t = 0; t < nk; ++t) any_cap |= out.cap[t] > 0;
+    if (any_cap) {
+        snn_exp_pairs_kernel<true><<<(unsigned)std::min<int64_t>(ccg_cdiv(n, 4), 16384), 256, 0, st>>>(n, sp, R.u, R.rows,
+                                                                                                      R.ex, out);
+        snn_exp_sort_kernel<<<(unsigned)std::min<int64_t>(ccg_cdiv((int64_t)nk * n, 4), 16384), 256, 0, st>>>(n, nk, R.ex,
+                                                                                                              out);
+        snn_exp_long_kernel<<<SNN_DENSE_BLOCKS, 256, 0, st>>>(n, R.ex, out, R.dense);
+    }
+    CCG_HIP(hipGetLastError());
+    return CCG_OK;
+}
+
+static int snn_edges_run(ccg_ctx* ctx, const int32_t* knn, int64_t n, int kstride, const int32_t* cell,
+                         const SnnSpec& sp, const SnnOut& out, int64_t* d_info, hipStream_t st) {
+    SnnExpRun R;
+    const int rc = snn_edges_count(ctx, knn, n, kstride, cell, sp, &R, st);
+    if (rc) return rc;
+    return snn_edges_emit(n, sp, R, out, d_info, st);
+}
+
+extern "C" int ccg_snn_edges_cells_dev(ccg_ctx* ctx, const int32_t* knn, int64_t n, int kstride, const int32_t* cell,
+                                       const int* ks, int nk, int32_t* const* out_i, int32_t* const* out_j,
+                                       double* const* out_w, const int64_t* caps, int64_t* d_info, void* stream) {
+    CCG_REQUIRE(ctx && knn && ks && d_info, "ccg_snn_edges_cells_dev: NULL argument");
+    CCG_REQUIRE(n >= 1 && n < (1LL << 31) - 1, "ccg_snn_edges_cells_dev: bad n");
+    SnnSpec sp;
+    int rc = snn_spec(ks, nk, CCG_SNN_NUMBER, kstride, &sp);
+    if (rc) return rc;
+    CCG_REQUIRE(snn_cls_ok(sp), "ccg_snn_edges_cells_dev: the smallest k must be <= 14 (4-bit class prefix fields)");
+    SnnOut out;
+    rc = snn_out_spec("ccg_snn_edges_cells_dev", nk, out_i, out_j, out_w, caps, &out);
+    if (rc) return rc;
+    hipStream_t st = ccg_pick_stream(ctx, stream);
+    const int t_all = ccg_timer_start(ctx, CCG_KT_SNN, st);
+    rc = snn_edges_run(ctx, knn, n, kstride, cell, sp, out, d_info, st);
+    if (rc) return rc;
+    ccg_timer_stop(ctx, t_all, st);
+    CCG_HIP(hipGetLastError());
+    return CCG_OK;
+}
+
 // ------------------------------------------------ host consumers (R, Python) --
 // What a host clustering call (igraph::make_graph + cluster_leiden, :656-658)
 // needs is every kNum graph as an edge list.  The device builds the graph
@@ -1868,6 +2293,17 @@ struct SnnStage {
     std::vector<int32_t> adj;
     std::vector<uint32_t> av;
     bool valid = false;
+    // the device-side edge lists of the last ccg_snn_edges_stage call (in
+    // WS_SNN_EDGES; ccg_snn_edges_fetch copies them out)
+    bool evalid = false;
+    int enk = 0;
+    int64_t ene[SNN_MAXK] = {0, 0, 0, 0};
+    int32_t* eoi[SNN_MAXK] = {nullptr, nullptr, nullptr, nullptr};
+    int32_t* eoj[SNN_MAXK] = {nullptr, nullptr, nullptr, nullptr};
+    double* eow[SNN_MAXK] = {nullptr, nullptr, nullptr, nullptr};
+    // the fetch's two pinned chunks and their copy events
+    void* pin[2] = {nullptr, nullptr};
+    hipEvent_t pev[2] = {nullptr, nullptr};
 };
 
 static void snn_stage_release(SnnStage* s) {
@@ -1880,6 +2316,13 @@ static void snn_stage_release(SnnStage* s) {
     s->wpk = nullptr;
     s->rcls = nullptr;
     s->cap_n = s->cap_l = s->cap_e = s->cap_w = s->cap_c = s->cap_r = 0;
+    for (int q = 0; q < 2; ++q) {
+        if (s->pin[q]) (void)hipHostFree(s->pin[q]);
+        if (s->pev[q]) (void)hipEventDestroy(s->pev[q]);
+        s->pin[q] = nullptr;
+        s->pev[q] = nullptr;
+    }
+    s->evalid = false;
 }
 
 void ccg_snn_stage_free(ccg_ctx* ctx) {
@@ -2253,6 +2696,206 @@ extern "C" int ccg_snn_graph_fetch(ccg_ctx* ctx, int t, int32_t* out_i, int32_t*
         }
     });
     clk.lap("fetch: rows");
+    return CCG_OK;
+}
+
+// ------------------------------------- host consumers, device emission --
+// ccg_snn_edges_stage / ccg_snn_edges_fetch: the same graphs as
+// ccg_snn_graphs_cells / ccg_snn_graph_fetch, but every graph's (i, j, w) list
+// is formed on the device (snn_edges_run; for RANK graphs or an input that
+// breaks the class contract, snn_build + snn_emit_kernel) into WS_SNN_EDGES,
+// and the fetch is a plain copy.
+
+// Graph t's lists inside the staging buffer (w first: 8-byte entries).
+static size_t snn_edges_layout(const int64_t* ne, int nk, size_t* ow, size_t* oi, size_t* oj) {
+    size_t b = 0;
+    for (int t = 0; t < nk; ++t) {
+        const size_t m = (size_t)std::max<int64_t>(ne[t], 1);
+        ow[t] = b;
+        b += (sizeof(double) * m + 255) & ~(size_t)255;
+        oi[t] = b;
+        b += (sizeof(int32_t) * m + 255) & ~(size_t)255;
+        oj[t] = b;
+        b += (sizeof(int32_t) * m + 255) & ~(size_t)255;
+    }
+    return b;
+}
+
+static int snn_edges_alloc(ccg_ctx* ctx, SnnStage* S, int nk, const int64_t* ne, SnnOut* out) {
+    size_t ow[SNN_MAXK], oi[SNN_MAXK], oj[SNN_MAXK];
+    const size_t bytes = snn_edges_layout(ne, nk, ow, oi, oj);
+    char* eb = (char*)ccg_ws(ctx, WS_SNN_EDGES, bytes);
+    if (!eb) return CCG_ENOMEM;
+    for (int t = 0; t < SNN_MAXK; ++t) {
+        const bool on = t < nk;
+        S->ene[t] = on ? ne[t] : 0;
+        S->eow[t] = on ? (double*)(eb + ow[t]) : nullptr;
+        S->eoi[t] = on ? (int32_t*)(eb + oi[t]) : nullptr;
+        S->eoj[t] = on ? (int32_t*)(eb + oj[t]) : nullptr;
+        out->cap[t] = S->ene[t];
+        out->ow[t] = S->eow[t];
+        out->oi[t] = S->eoi[t];
+        out->oj[t] = S->eoj[t];
+    }
+    S->enk = nk;
+    return CCG_OK;
+}
+
+extern "C" int ccg_snn_edges_stage(ccg_ctx* ctx, const int32_t* knn, int64_t n, int kstride, const int32_t* cell,
+                                   const int* ks, int nk, int type, int64_t* nedges) {
+    CCG_REQUIRE(ctx && knn && ks && nedges, "ccg_snn_edges_stage: NULL argument");
+    CCG_REQUIRE(n >= 1 && n < (1LL << 31) - 1 && kstride >= 1, "ccg_snn_edges_stage: bad sizes");
+    SnnSpec sp;
+    int rc = snn_spec(ks, nk, type, kstride, &sp);
+    if (rc) return rc;
+    for (int64_t t = 0; t < n * kstride; ++t)
+        CCG_REQUIRE(knn[t] >= 0 && knn[t] < n && knn[t] != t / kstride,
+                    "ccg_snn_edges_stage: neighbour index out of range or self at %lld", (long long)t);
+    CCG_HIP(hipSetDevice(ctx->device));
+    if (!ctx->snn_stage) ctx->snn_stage = new SnnStage();
+    SnnStage* S = (SnnStage*)ctx->snn_stage;
+    S->evalid = false;
+    hipStream_t st = ctx->stream;
+    const int kmax = sp.kk[nk - 1];
+    int32_t* dknn = (int32_t*)ccg_ws(ctx, WS_HOST_A, sizeof(int32_t) * n * kstride);
+    int32_t* dcell = cell ? (int32_t*)ccg_ws(ctx, WS_HOST_B, sizeof(int32_t) * n) : nullptr;
+    int64_t* dinfo = (int64_t*)ccg_ws(ctx, WS_HOST_E, 256);
+    if (!dknn || (cell && !dcell) || !dinfo) return CCG_ENOMEM;
+    CCG_HIP(hipMemcpyAsync(dknn, knn, sizeof(int32_t) * n * kstride, hipMemcpyHostToDevice, st));
+    if (cell) CCG_HIP(hipMemcpyAsync(dcell, cell, sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
+    bool classes = snn_cls_ok(sp);
+    for (int attempt = 0; attempt < 3; ++attempt) {
+        SnnOut out;
+        rc = snn_out_spec("ccg_snn_edges_stage", nk, nullptr, nullptr, nullptr, nullptr, &out);
+        if (rc) return rc;
+        int64_t info[3 + SNN_MAXK] = {0, 0, 0, 0, 0, 0, 0};
+        int64_t ne[SNN_MAXK] = {0, 0, 0, 0};
+        if (classes) {
+            // the count phase and its d_info, then the emission into buffers of the counted sizes
+            SnnExpRun R;
+            rc = snn_edges_count(ctx, dknn, n, kstride, dcell, sp, &R, st);
+            if (!rc) rc = snn_edges_emit(n, sp, R, out, dinfo, st);
+            if (rc) return rc;
+            CCG_HIP(hipMemcpyAsync(info, dinfo, sizeof(int64_t) * (3 + nk), hipMemcpyDeviceToHost, st));
+            rc = ccg_take_device_error(ctx);  // synchronises
+            if (rc) return rc;
+            if (info[1] != 0) {  // the input breaks the class contract: the row-level pass
+                classes = false;
+                continue;
+            }
+            if (info[3] < 0) {  // the class rows did not fit the reservation: grow it and rerun
+                ctx->snn_row_reserve = info[2] + info[2] / 8;
+                continue;
+            }
+            for (int t = 0; t < nk; ++t) ne[t] = info[3 + t];
+            rc = snn_edges_alloc(ctx, S, nk, ne, &out);
+            if (rc) return rc;
+            rc = snn_edges_emit(n, sp, R, out, dinfo, st);
+            if (rc) return rc;
+            CCG_HIP(hipMemcpyAsync(info, dinfo, sizeof(int64_t) * (3 + nk), hipMemcpyDeviceToHost, st));
+            CCG_HIP(hipStreamSynchronize(st));
+            for (int t = 0; t < nk; ++t)
+                CCG_REQUIRE(info[3 + t] == ne[t], "ccg_snn_edges_stage: internal count mismatch (%lld vs %lld)",
+                            (long long)info[3 + t], (long long)ne[t]);
+        } else {
+            const int64_t rcap =
+                ctx->snn_row_reserve > 0 ? ctx->snn_row_reserve : (int64_t)SNN_ROW_RESERVE * n * (kmax + 1);
+            char* rbuf = (char*)ccg_ws(ctx, WS_SNN_ROWS,
+                                       (sizeof(int32_t) + sizeof(uint32_t)) * rcap + sizeof(int32_t) * (n + 64));
+            if (!rbuf) return CCG_ENOMEM;
+            int32_t* nbr = (int32_t*)rbuf;
+            uint32_t* wpk = (uint32_t*)(nbr + rcap);
+            int32_t* rlen = (int32_t*)(wpk + rcap);
+            int64_t* cnt = nullptr;
+            const int64_t* roff = nullptr;
+            rc = snn_build(ctx, dknn, n, kstride, sp, st, nbr, wpk, rcap, nullptr, rlen, &cnt, &roff);
+            if (rc) return rc;
+            snn_copy_totals<<<1, 64, 0, st>>>(cnt, n, nk, roff, rcap, dinfo, nk > 1 ? dinfo + 1 : nullptr,
+                                              nk > 2 ? dinfo + 2 : nullptr, nk > 3 ? dinfo + 3 : nullptr);
+            CCG_HIP(hipGetLastError());
+            CCG_HIP(hipMemcpyAsync(ne, dinfo, sizeof(int64_t) * nk, hipMemcpyDeviceToHost, st));
+            rc = ccg_take_device_error(ctx);  // synchronises
+            if (rc) return rc;
+            if (ne[0] < 0) {
+                ctx->snn_row_reserve = -ne[0] + -ne[0] / 8;
+                continue;
+            }
+            rc = snn_edges_alloc(ctx, S, nk, ne, &out);
+            if (rc) return rc;
+            const SnnRows rows{roff, rlen, nbr, wpk, rcap};
+            snn_emit_kernel<<<(unsigned)std::min<int64_t>(ccg_cdiv(n, 4), 16384), 256, 0, st>>>(n, sp, cnt, rows, out);
+            CCG_HIP(hipGetLastError());
+            CCG_HIP(hipStreamSynchronize(st));
+        }
+        for (int t = 0; t < nk; ++t) nedges[t] = ne[t];
+        S->evalid = true;
+        return CCG_OK;
+    }
+    ccg_set_error("ccg_snn_edges_stage: row reservation could not be satisfied");
+    return CCG_ENOMEM;
+}
+
+// Device -> pageable host memory through two pinned chunks: while the DMA
+// fills one, host threads copy the other out (the first touch of a fresh
+// destination is most of that copy, so it is split over threads).
+#define SNN_FETCH_CHUNK ((size_t)32 << 20)
+#define SNN_FETCH_THREADS 16
+#define SNN_FETCH_PINNED_DEFAULT true
+static int snn_fetch_pinned(ccg_ctx* ctx, SnnStage* S, void* dst, const void* src, size_t bytes) {
+    for (int q = 0; q < 2; ++q) {
+        if (!S->pin[q]) CCG_HIP(hipHostMalloc(&S->pin[q], SNN_FETCH_CHUNK, hipHostMallocDefault));
+        if (!S->pev[q]) CCG_HIP(hipEventCreateWithFlags(&S->pev[q], hipEventDisableTiming));
+    }
+    hipStream_t st = ctx->stream;
+    const size_t nch = (bytes + SNN_FETCH_CHUNK - 1) / SNN_FETCH_CHUNK;
+    auto len = [&](size_t c) { return std::min(SNN_FETCH_CHUNK, bytes - c * SNN_FETCH_CHUNK); };
+    auto issue = [&](size_t c) -> hipError_t {
+        hipError_t e = hipMemcpyAsync(S->pin[c & 1], (const char*)src + c * SNN_FETCH_CHUNK, len(c),
+                                      hipMemcpyDeviceToHost, st);
+        return e != hipSuccess ? e : hipEventRecord(S->pev[c & 1], st);
+    };
+    CCG_HIP(issue(0));
+    for (size_t c = 0; c < nch; ++c) {
+        if (c + 1 < nch) CCG_HIP(issue(c + 1));  // (its chunk was copied out in the previous round)
+        CCG_HIP(hipEventSynchronize(S->pev[c & 1]));
+        char* d = (char*)dst + c * SNN_FETCH_CHUNK;
+        const char* p = (const char*)S->pin[c & 1];
+        snn_host_parallel((int64_t)len(c), SNN_FETCH_THREADS,
+                          [&](int64_t b0, int64_t b1) { std::memcpy(d + b0, p + b0, (size_t)(b1 - b0)); });
+    }
+    return CCG_OK;
+}
+
+extern "C" int ccg_snn_edges_fetch(ccg_ctx* ctx, int t, int32_t* out_i, int32_t* out_j, double* out_w, int64_t cap) {
+    CCG_REQUIRE(ctx, "ccg_snn_edges_fetch: NULL ctx");
+    SnnStage* S = (SnnStage*)ctx->snn_stage;
+    CCG_REQUIRE(S && S->evalid, "ccg_snn_edges_fetch: no graphs staged (call ccg_snn_edges_stage first)");
+    CCG_REQUIRE(t >= 0 && t < S->enk, "ccg_snn_edges_fetch: graph %d of %d", t, S->enk);
+    const int64_t ne = S->ene[t];
+    if (cap < ne) {
+        ccg_set_error("ccg_snn_edges_fetch: capacity %lld < %lld edges", (long long)cap, (long long)ne);
+        return CCG_ECAP;
+    }
+    if (ne == 0) return CCG_OK;
+    CCG_HIP(hipSetDevice(ctx->device));
+    const char* mode = std::getenv("CCG_SNN_FETCH");  // tools and tuning only: "pinned" / "direct"
+    const bool pinned = mode ? std::strcmp(mode, "pinned") == 0 : SNN_FETCH_PINNED_DEFAULT;
+    struct {
+        void* dst;
+        const void* src;
+        size_t bytes;
+    } parts[3] = {{out_i, S->eoi[t], sizeof(int32_t) * (size_t)ne},
+                  {out_j, S->eoj[t], sizeof(int32_t) * (size_t)ne},
+                  {out_w, S->eow[t], sizeof(double) * (size_t)ne}};
+    for (auto& p : parts) {
+        if (!p.dst) continue;
+        if (pinned && p.bytes >= 2 * SNN_FETCH_CHUNK) {
+            const int rc = snn_fetch_pinned(ctx, S, p.dst, p.src, p.bytes);
+            if (rc) return rc;
+        } else {
+            CCG_HIP(hipMemcpy(p.dst, p.src, p.bytes, hipMemcpyDeviceToHost));
+        }
+    }
     return CCG_OK;
 }
 

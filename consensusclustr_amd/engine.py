@@ -220,19 +220,32 @@ class Engine:
         check(self.lib.ccg_snn_graph_fetch(self.ctx, t, _ptr(ei), _ptr(ej), _ptr(w), m))
         return ei, ej, w
 
-    def snn_multi(self, knn_idx, ks, type="number", cell=None):
+    def _snn_edges_fetch(self, t, m):
+        ei = np.empty(m, np.int32)
+        ej = np.empty(m, np.int32)
+        w = np.empty(m, np.float64)
+        check(self.lib.ccg_snn_edges_fetch(self.ctx, t, _ptr(ei), _ptr(ej), _ptr(w), m))
+        return ei, ej, w
+
+    def snn_multi(self, knn_idx, ks, type="number", cell=None, emit="host"):
         """The graph of every k in ks (any order, repeats allowed) from one
-        device pass per 4 distinct values (ccg_snn_graphs_cells: class-level
-        rows for NUMBER graphs, union rows otherwise, staged on the host;
-        ccg_snn_graph_fetch decodes each graph).  cell: the cell of every
-        bootstrap row (copies share one; None = unknown).  Returns a list of
-        (i, j, w) edge lists aligned with ks."""
+        device pass per 4 distinct values.  emit="host" (the default):
+        ccg_snn_graphs_cells stages class-level rows for NUMBER graphs, union
+        rows otherwise, on the host and ccg_snn_graph_fetch decodes each graph
+        there.  emit="device": ccg_snn_edges_stage forms every edge list on
+        the device and ccg_snn_edges_fetch copies it out (the same lists).
+        cell: the cell of every bootstrap row (copies share one; None =
+        unknown).  Returns a list of (i, j, w) edge lists aligned with ks."""
+        if emit not in ("host", "device"):
+            raise ValueError(f"snn_multi: emit must be 'host' or 'device', not {emit!r}")
         knn_idx = np.ascontiguousarray(knn_idx, dtype=np.int32)
         n, kst = knn_idx.shape
         t = {"number": _lib.CCG_SNN_NUMBER, "rank": _lib.CCG_SNN_RANK}[type]
         cl = None if cell is None else np.ascontiguousarray(cell, dtype=np.int32).ravel()
         if cl is not None and cl.size != n:  # the library reads n entries
             raise ValueError(f"snn_multi: cell has {cl.size} entries, knn_idx has {n} rows")
+        stage = self.lib.ccg_snn_graphs_cells if emit == "host" else self.lib.ccg_snn_edges_stage
+        fetch = self._snn_fetch if emit == "host" else self._snn_edges_fetch
         uk = sorted({int(k) for k in ks})
         got = {}
         t_pass = t_fetch = 0.0
@@ -241,15 +254,16 @@ class Engine:
             nk = len(chunk)
             ne = (ctypes.c_int64 * nk)()
             t0 = time.perf_counter()
-            check(self.lib.ccg_snn_graphs_cells(self.ctx, _ptr(knn_idx), n, kst, _ptr(cl),
-                                                (ctypes.c_int * nk)(*chunk), nk, t, ne))
+            check(stage(self.ctx, _ptr(knn_idx), n, kst, _ptr(cl), (ctypes.c_int * nk)(*chunk), nk, t, ne))
             t1 = time.perf_counter()
             for g, k in enumerate(chunk):
-                got[k] = self._snn_fetch(g, ne[g])
+                got[k] = fetch(g, ne[g])
             t_pass += t1 - t0
             t_fetch += time.perf_counter() - t1
-        # host seconds: the device pass with its copies to pinned memory, then
-        # the host expansion of the class rows into the per-graph edge lists
+        # host seconds.  emit="host": the device pass with its copies to pinned
+        # memory, then the host expansion of the class rows into the per-graph
+        # edge lists.  emit="device": (stage, fetch) -- the device pass with the
+        # expansion, then the copies of the finished lists.
         self.last_snn_times = (t_pass, t_fetch)
         return [got[int(k)] for k in ks]
 
@@ -567,6 +581,29 @@ class Engine:
         check(self.lib.ccg_snn_classes_dev(self.ctx, _ptr(knn_idx), n, kst, _ptr(cell), karr, nk, _ptr(row_class),
                                            _ptr(class_root), _ptr(class_off), _ptr(class_len), _ptr(nbr), _ptr(wpk),
                                            nbr.numel(), _ptr(d_info), _stream()))
+
+    def snn_edges_cells_t(self, knn_idx, ks, outs, d_info, cell=None, caps=None):
+        """The NUMBER graphs of ks (ascending) as row-level edge lists expanded
+        from the class rows on the device (ccg_snn_edges_cells_dev).  outs: per
+        graph (i, j, w) tensors (int32, int32, float64; capacity = numel) or
+        None for count-only; d_info (3 + len(ks),) int64 = [u, status, required
+        class-row capacity, E_t per graph (negative = -(required capacity):
+        grow snn_reserve)]; cell (n,) int32 tensor or None.  Graph t is written
+        only when status is 0 and 0 <= E_t <= its capacity.  caps: capacities
+        below the tensors' sizes (all 0: count only)."""
+        n, kst = knn_idx.shape
+        nk = len(ks)
+        karr = (ctypes.c_int * nk)(*ks)
+        P = _vp * nk
+        oi = P(*[_ptr(o[0]) if o else None for o in outs])
+        oj = P(*[_ptr(o[1]) if o else None for o in outs])
+        ow = P(*[_ptr(o[2]) if o else None for o in outs])
+        full = [min(x.numel() for x in o) if o else 0 for o in outs]
+        if caps is not None and any(int(c) > f for c, f in zip(caps, full)):
+            raise ValueError("snn_edges_cells_t: caps exceed the output tensors")
+        caps = (ctypes.c_int64 * nk)(*(full if caps is None else [int(c) for c in caps]))
+        check(self.lib.ccg_snn_edges_cells_dev(self.ctx, _ptr(knn_idx), n, kst, _ptr(cell), karr, nk, oi, oj, ow,
+                                               caps, _ptr(d_info), _stream()))
 
     def snn_reserve(self, entries):
         check(self.lib.ccg_snn_reserve(self.ctx, entries))

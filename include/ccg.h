@@ -406,6 +406,43 @@ int ccg_snn_classes_dev(ccg_ctx* ctx, const int32_t* knn, int64_t n, int kstride
                         int32_t* class_len, int32_t* nbr, uint32_t* wpk, int64_t cap, int64_t* d_info,
                         void* stream);
 
+/* The NUMBER graphs of ccg_snn_classes_dev expanded ON THE DEVICE into each
+ * graph's row-level edge list: edges i < j sorted by (i, j), weights as
+ * ccg_snn -- bit for bit what ccg_snn_graph_fetch decodes on the host, and the
+ * same between runs.  The class rows live in the context's row reservation
+ * (ccg_snn_reserve, as for ccg_snn_multi_dev); row x of class C gets every row
+ * y > x of C (weight ks[t] + 1) and every row y > x of each class adjacent to C
+ * in graph t (the class weight), each row's list sorted by y on the device.
+ *   cell   : device, n entries or NULL (see ccg_snn_classes_dev)
+ *   out_*  : nk device lists of capacity caps[t] (host array; entries may be
+ *            NULL where caps[t] == 0)
+ *   d_info : device int64, 3 + nk: u, status (0: valid; 1: the input breaks
+ *            the class contract -- nothing is written and the counts are 0;
+ *            use ccg_snn_multi_dev), required class-row capacity, then per
+ *            graph E_t = its row-level edge count, or -(required class-row
+ *            capacity) when the class rows did not fit the reservation.
+ * Graph t is written only when status is 0, the class rows fit and
+ * E_t <= caps[t]; otherwise nothing of graph t is written (caps all 0: the
+ * call only counts).  Requires ks ascending, nk <= 4, ks[0] <= 14, n < 2^21.
+ * No host synchronisation. */
+int ccg_snn_edges_cells_dev(ccg_ctx* ctx, const int32_t* knn, int64_t n, int kstride, const int32_t* cell,
+                            const int* ks, int nk, int32_t* const* out_i, int32_t* const* out_j,
+                            double* const* out_w, const int64_t* caps, int64_t* d_info, void* stream);
+
+/* ccg_snn_graphs_cells / ccg_snn_graph_fetch with the edge lists formed on the
+ * device: stage validates and uploads knn and cell (host), runs the class
+ * pass and the device expansion (for RANK graphs or an input that breaks the
+ * class contract the row-level pass and its device emission) into device
+ * buffers owned by the context (freed with it), growing the row reservation
+ * on demand, and returns every graph's edge count in nedges (host, nk
+ * entries).  fetch copies graph t to caller memory (pageable is fine): any
+ * output may be NULL, cap < the edge count returns CCG_ECAP, and it may be
+ * called any number of times until the next ccg_snn_edges_stage call.  The
+ * lists equal ccg_snn_graph_fetch's bit for bit.  Both synchronise. */
+int ccg_snn_edges_stage(ccg_ctx* ctx, const int32_t* knn, int64_t n, int kstride, const int32_t* cell,
+                        const int* ks, int nk, int type, int64_t* nedges);
+int ccg_snn_edges_fetch(ccg_ctx* ctx, int t, int32_t* out_i, int32_t* out_j, double* out_w, int64_t cap);
+
 /* Row entries the per-graph functions reserve in the context workspace
  * (0 = the default 40 n (kmax+1)); ccg_snn grows it on demand, the _dev
  * functions report -(required) in d_nedges instead. */
