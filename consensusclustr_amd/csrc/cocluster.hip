@@ -907,6 +907,10 @@ extern "C" int ccg_consensus_knn_dev(ccg_ctx* ctx, const uint16_t* co, const uin
 #ifndef CKC_SAMPLE
 #define CKC_SAMPLE 4096
 #endif
+// (ckc_tau_kernel packs a row's bucket counts into 16 bits: a row past the
+// sample counts every one of its NS <= CKC_SAMPLE columns, possibly all into
+// one bucket)
+static_assert(CKC_SAMPLE < 65536, "ckc_tau_kernel keeps 16-bit bucket counts: a bucket may hold CKC_SAMPLE values");
 #define CKC_CAP 2048
 #define CKC_MIN_N 32768
 
@@ -936,8 +940,11 @@ __global__ void ckc_permute_kernel(const T* __restrict__ A, int64_t N, int64_t B
 // 2 / CKC_NBK, a few more candidates per row.
 __global__ __launch_bounds__(256) void ckc_tau_kernel(const uint32_t* __restrict__ cb, int64_t a, int64_t b,
                                                       int64_t NS, int k, int* __restrict__ tnum) {
-    // two 16-bit bucket counts per LDS word (a row counts at most NS <= 2^16
-    // values): 8 KB per wave instead of 16, so 5 blocks per CU instead of 2
+    // two 16-bit bucket counts per LDS word (a row counts at most NS <=
+    // CKC_SAMPLE < 2^16 values, all of which may tie in one bucket -- 2^16
+    // itself would carry into the neighbouring count; see the static_assert
+    // at CKC_SAMPLE): 8 KB per wave instead of 16, so 5 blocks per CU instead
+    // of 2
     __shared__ __attribute__((aligned(16))) unsigned hist[4][CKC_NBK / 2];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t row = a + (int64_t)blockIdx.x * 4 + wv;
@@ -1155,14 +1162,36 @@ extern "C" int ccg_consensus_knn_assign_dev(ccg_ctx* ctx, const void* A, int lab
     CCG_REQUIRE(r0 % CCG_COCLUSTER_ROW_ALIGN == 0, "ccg_consensus_knn_assign_dev: r0 must be a multiple of %d",
                 CCG_COCLUSTER_ROW_ALIGN);
     const int t_k = ccg_timer_start(ctx, CCG_KT_COCLUSTER, st);
-    const char* path = getenv("CCG_CKNN_PATH");  // tools/tests: "slab" forces the sub-slab path
-    if (r0 == 0 && r1 == N && N >= CKC_MIN_N && B <= COF_CHUNK && !(path && !strcmp(path, "slab"))) {
+    // tools/tests (read per call): "slab" forces the sub-slab path; "cand"
+    // makes a call that does not finish on the candidate path -- not eligible,
+    // a row overflowed its list, or more than one column chunk -- return
+    // CCG_ECAP instead of falling back, so a test knows which path it compared
+    const char* path = getenv("CCG_CKNN_PATH");
+    const bool want_cand = path && !strcmp(path, "cand");
+    const bool eligible = r0 == 0 && r1 == N && N >= CKC_MIN_N && B <= COF_CHUNK;
+    if (want_cand && !eligible) {
+        ccg_set_error(
+            "ccg_consensus_knn_assign_dev: CCG_CKNN_PATH=cand, but the candidate path takes only whole matrices with "
+            "N >= %d and B <= %d",
+            CKC_MIN_N, COF_CHUNK);
+        ccg_timer_stop(ctx, t_k, st);
+        return CCG_ECAP;
+    }
+    if (eligible && !(path && !strcmp(path, "slab"))) {
         bool done = false;
         int rc = ckc_run(ctx, A, label_bits, N, B, k, out_idx, d_nan_flag, st, &done);
         if (rc) return rc;
         if (done) {
             ccg_timer_stop(ctx, t_k, st);
             return CCG_OK;
+        }
+        if (want_cand) {
+            ccg_set_error(
+                "ccg_consensus_knn_assign_dev: CCG_CKNN_PATH=cand, but the candidate path did not finish (a row with "
+                "more than %d candidates, or more than one column chunk)",
+                CKC_CAP);
+            ccg_timer_stop(ctx, t_k, st);
+            return CCG_ECAP;
         }
         CCG_HIP(hipMemsetAsync(d_nan_flag, 0, sizeof(int32_t), st));
     }

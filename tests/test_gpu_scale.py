@@ -165,7 +165,7 @@ def test_consensus_knn_candidate_path_equals_subslab_path_with_fallback(engine, 
     At = _robust_A(71, B, N, pop)
     k = 20
     outs = []
-    for path in ("", "slab"):
+    for path in ("cand", "slab"):  # ("cand": a call that falls back returns an error instead)
         monkeypatch.setenv("CCG_CKNN_PATH", path)
         out = torch.full((N, k), -1, dtype=torch.int32, device="cuda")
         flag = torch.zeros(1, dtype=torch.int32, device="cuda")
